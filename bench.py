@@ -6,7 +6,11 @@ LibriSpeech-shaped spectrogram batches with random-init weights (no dataset/chec
 is available offline). Every step is a full training step: forward, CTC loss, backward,
 RCCL gradient all-reduce (N > 1), fused Adam + weight EMA.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps and prints one JSON line. --full adds the
+  secondary measurements after the timed region (SortaGrad epoch walk, streaming-inference
+  RTF). --dump-outputs DIR writes what the last timed step left (loss, weights, EMA, Adam
+  first moment) as DIR/<name>.npy, to compare two builds output for output.
   (N > 1: either bench.py starts the N ranks itself, or an outer launcher does:
    python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...;
    a --gpus that disagrees with the launcher's WORLD_SIZE is an error)
@@ -63,12 +67,20 @@ def parse():
     p.add_argument("--dp_graphs", action="store_true",
                    help="data parallel: the epoch walk's per-shape step graphs capture the bucketed "
                         "step too (Trainer dp_graphs)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline timing also measure the SortaGrad epoch walk and the "
+                        "streaming-inference RTF (result line: epoch_walk, inference); a plain run "
+                        "does neither")
+    p.add_argument("--dump-outputs", dest="dump_outputs", type=str, default="", metavar="DIR",
+                   help="after the timed steps write what the last one left (loss, and fixed seeded "
+                        "samples of the weights, their EMA and Adam's first moment) as DIR/<name>.npy "
+                        "(float32; rank 0)")
     p.add_argument("--no_infer", action="store_true",
-                   help="skip the streaming-inference RTF measured after the training timing "
-                        "(BASELINE metric's inference half; rank 0, outside the timed region)")
+                   help="with --full: skip the streaming-inference RTF measured after the training "
+                        "timing (BASELINE metric's inference half; rank 0, outside the timed region)")
     p.add_argument("--infer_seconds", type=float, default=10.0, help="audio per stream of the RTF runs")
     p.add_argument("--no_walk", action="store_true",
-                   help="skip the SortaGrad epoch walk measured after the headline timing")
+                   help="with --full: skip the SortaGrad epoch walk measured after the headline timing")
     p.add_argument("--walk_scale", type=int, default=1,
                    help="epoch-walk size: the reference dummy epoch's bucket counts x this (reference: 10)")
     p.add_argument("--no_defer_update", action="store_true",
@@ -180,18 +192,20 @@ def main():
         RNN.check_errors()
     elapsed = ctx.all_reduce_max(elapsed)
     total_audio = ctx.all_reduce_sum(audio)
-    ms = 1000.0 * elapsed / args.steps
+    ms = 1000.0 * elapsed / max(args.steps, 1)
     value = total_audio / elapsed
     flops = ctx.all_reduce_sum(flops)
     lossv = float(loss.float().item()) if loss is not None else float("nan")
     # device memory high-water mark of the headline steps (caching allocator; this rank)
     peak_gib = torch.cuda.max_memory_allocated(dev) / 2 ** 30 if dev.type == "cuda" else None
+    if args.dump_outputs and ctx.is_main:
+        dump_outputs(args.dump_outputs, trainer, loss)
     walk = None
-    if not args.no_walk and dev.type == "cuda":
+    if args.full and not args.no_walk and dev.type == "cuda":
         walk = epoch_walk(trainer, ctx, dev, args.batch_size, args.walk_scale)
     shutdown(ctx)
     infer = None
-    if ctx.is_main and not args.no_infer:
+    if args.full and ctx.is_main and not args.no_infer:
         infer = streaming_rtf(dev, args.engine, args.infer_seconds)
     if ctx.is_main:
         out = {
@@ -227,6 +241,42 @@ def main():
         if infer is not None:
             out["inference"] = infer
         print(json.dumps(out), flush=True)
+
+
+_DUMP_SAMPLE = 2 * 2 ** 20     # elements kept of each flat state array (8 MiB as float32)
+
+
+def dump_outputs(out_dir: str, trainer, loss) -> None:
+    """What a caller of the timed path holds after its last step, as float32 <name>.npy files:
+    the step's loss, and the training state the step updated — weights, their EMA and Adam's
+    first moment (a running mean of the gradients, so the backward pass shows too). The
+    carried optimizer update has been flushed inside the timed region. A state array larger
+    than _DUMP_SAMPLE elements is written as a fixed sample: the same sorted indices
+    (sample_index.npy as float64, seed 0) for every array and every run, 40 MiB in all."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, arr):
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+    lossv = loss.detach().float().reshape(-1).cpu().numpy() if loss is not None else np.zeros(0, np.float32)
+    save("loss", lossv.astype(np.float32))
+    flat = trainer.arena.flat
+    n = flat.numel()
+    idx = None
+    if n > _DUMP_SAMPLE:
+        pick = np.sort(np.random.default_rng(0).choice(n, _DUMP_SAMPLE, replace=False))
+        save("sample_index", pick.astype(np.float64))        # exact: indices < 2^53
+        idx = torch.from_numpy(pick.astype(np.int64)).to(flat.device)
+    state = {"weights": flat, "adam_m": trainer.opt.m}
+    if trainer.opt.ema is not None:
+        state["weights_ema"] = trainer.opt.ema
+    for name, t in state.items():
+        t = t.detach().reshape(-1)
+        if idx is not None:
+            t = t.index_select(0, idx)
+        save(name, t.float().cpu().numpy())
 
 
 def epoch_walk(trainer, ctx, dev, batch_size: int, scale: int):

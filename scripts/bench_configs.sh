@@ -8,7 +8,7 @@ set -o pipefail
 out=${1:-gpurun_out/configs}
 mkdir -p "$out"
 export TMPDIR=/tmp
-run() { local name=$1; shift; timeout -k 10 180 python bench.py "$@" --steps 20 --warmup 5 --no_infer > "$out/$name.log" 2>&1; }
+run() { local name=$1; shift; timeout -k 10 180 python bench.py "$@" --steps 20 --warmup 5 --full --no_infer >"$out/$name.log" 2>&1; }
 run c5_bf16 --num_hidden 1280 --num_rnn_layers 7 &&
 run c5_fp8 --num_hidden 1280 --num_rnn_layers 7 --fp8 &&
 run ref1760 --cell rnn_relu --num_hidden 1760 --num_rnn_layers 7 &&

@@ -166,7 +166,7 @@ def _run_bench(nproc, extra_env, args, timeout=600):
 def test_bench_two_ranks_json_contract():
     """bench.py under torch.distributed.run with 2 ranks (gloo on CPU): one JSON line, whole-job
     aggregate value (summed audio / max elapsed), n_gpus and dp degree reported."""
-    out = _run_bench(2, {"CUDA_VISIBLE_DEVICES": ""},
+    out = _run_bench(2, {"CUDA_VISIBLE_DEVICES": "", "HIP_VISIBLE_DEVICES": ""},
                      ["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch_size", "2", "--frames", "200",
                       "--num_hidden", "32", "--num_rnn_layers", "1", "--num_filters", "4", "--no_infer"])
     assert out["n_gpus"] == 2 and out["steps"] == 2 and out["warmup"] == 1
@@ -182,7 +182,7 @@ def test_bench_two_ranks_json_contract():
 
 def _run_bench_direct(args, timeout=600):
     import json
-    env = dict(os.environ, PYTHONPATH=ROOT, OMP_NUM_THREADS="2", CUDA_VISIBLE_DEVICES="")
+    env = dict(os.environ, PYTHONPATH=ROOT, OMP_NUM_THREADS="2", CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, cwd=ROOT,
@@ -197,8 +197,9 @@ _TINY_NOINF = _TINY + ["--no_infer"]
 
 def test_bench_gpus_flag_spawns_ranks_without_launcher():
     """python bench.py --gpus 2 (no torchrun): bench.py starts the two ranks itself
-    (parallel/launch.py) and rank 0 prints one JSON line for the 2-rank job."""
-    r, rows = _run_bench_direct(["--gpus", "2", "--infer_seconds", "1"] + _TINY)
+    (parallel/launch.py) and rank 0 prints one JSON line for the 2-rank job; --full adds the
+    inference half."""
+    r, rows = _run_bench_direct(["--gpus", "2", "--full", "--infer_seconds", "1"] + _TINY)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert len(rows) == 1, r.stdout
     out = rows[0]
@@ -212,7 +213,7 @@ def test_bench_gpus_flag_spawns_ranks_without_launcher():
 
 def test_bench_gpus_mismatch_with_launcher_fails():
     """--gpus 3 under a 2-rank torchrun is an error, not a silent 2-rank run."""
-    env = dict(os.environ, PYTHONPATH=ROOT, OMP_NUM_THREADS="2", CUDA_VISIBLE_DEVICES="")
+    env = dict(os.environ, PYTHONPATH=ROOT, OMP_NUM_THREADS="2", CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "3"] + _TINY_NOINF
@@ -261,7 +262,7 @@ def test_allreduce_bandwidth_tool_two_ranks():
     """tools/bench_allreduce.py (nccl-tests conventions) under torch.distributed.run, 2 CPU
     ranks over gloo: one JSON line per size on rank 0 with busbw = algbw * 2(n-1)/n."""
     import json
-    env = dict(os.environ, PYTHONPATH=ROOT, OMP_NUM_THREADS="2", CUDA_VISIBLE_DEVICES="")
+    env = dict(os.environ, PYTHONPATH=ROOT, OMP_NUM_THREADS="2", CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "tools", "bench_allreduce.py"), "--device", "cpu", "--sizes_mb", "1,2",

@@ -85,7 +85,7 @@ def main(argv=None) -> int:
         os.makedirs(a.out, exist_ok=True)
     env_note = {}
     if a.cpu:
-        os.environ["CUDA_VISIBLE_DEVICES"] = ""
+        os.environ["CUDA_VISIBLE_DEVICES"] = os.environ["HIP_VISIBLE_DEVICES"] = ""
         env_note["backend"] = "gloo (cpu)"
     rows = []
     for w in worlds:
