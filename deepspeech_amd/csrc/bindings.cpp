@@ -239,6 +239,24 @@ int ds2_nonfinite_watch(const float* loss, int* counter, int* first_bad, hipStre
 int ds2_spin(long long ticks, int blocks, int threads, int lds_bytes, int* done, hipStream_t st);
 int ds2_fc_logits(const void* h, const void* W, const void* bias, void* logits, int out_bf16, int M, int H, int K,
                   hipStream_t st);
+struct DS2Feat {          // csrc/featurize.hip
+  const void* pcm;
+  long long row_stride;
+  int S, lead, mode, B, T_max;
+  const int* lens;
+  const float* offset;
+  const float* gain;
+  const float* basis;
+  const int* mel_idx;
+  const float* mel_w;
+  const float* dct;
+  const float* lifter;
+  void* out;
+  int* frames;
+};
+int ds2_audio_stats(const void* pcm, int in_i16, long long row_stride, int S, int B, const int* lens, float* offset,
+                    float* gain, hipStream_t st);
+int ds2_featurize(const DS2Feat* a, int kind, int in_i16, int out_bf16, hipStream_t st);
 }
 
 namespace {
@@ -1505,6 +1523,75 @@ void fc_logits(at::Tensor h, at::Tensor W, at::Tensor bias, at::Tensor logits) {
         "fc_logits");
 }
 
+// --------------------------------------------------------------------------- audio features (csrc/featurize.hip)
+int pcm_is_i16(const at::Tensor& pcm) {
+  need_gpu(pcm, "pcm");
+  TORCH_CHECK(pcm.dim() == 2, "pcm must be [B, S]");
+  if (pcm.scalar_type() == at::kShort) return 1;
+  TORCH_CHECK(pcm.scalar_type() == at::kFloat, "pcm must be float32 or int16");
+  return 0;
+}
+
+const int* feat_lens(const OptT& lens, int64_t B) {
+  const int* p = ptr_or_null<const int>(lens, "lens");
+  if (p) TORCH_CHECK(lens->scalar_type() == at::kInt && lens->numel() == B, "lens must be int32 [B]");
+  return p;
+}
+
+// per-row offset = mean(x) and gain = 1 / max|x - mean| (1 when the peak is 0), on the device
+void audio_stats(at::Tensor pcm, OptT lens, at::Tensor offset, at::Tensor gain) {
+  const int i16 = pcm_is_i16(pcm);
+  const int64_t B = pcm.size(0), S = pcm.size(1);
+  TORCH_CHECK(S < (1LL << 31), "audio_stats: row too long");
+  need_gpu(offset, "offset");
+  need_gpu(gain, "gain");
+  TORCH_CHECK(offset.scalar_type() == at::kFloat && offset.numel() == B && gain.scalar_type() == at::kFloat &&
+                  gain.numel() == B, "offset / gain must be fp32 [B]");
+  check(ds2_audio_stats(pcm.data_ptr(), i16, S, (int)S, (int)B, feat_lens(lens, B), offset.data_ptr<float>(),
+                        gain.data_ptr<float>(), cur_stream()),
+        "audio_stats");
+}
+
+// kind 0 = mfcc (tables: basis [400, 512], mel_idx [322, 2], mel_w [322, 8], dct [322, 192], lifter [161]),
+// kind 1 = spectrogram (basis [320, 320] with the window folded in). lead = 1: pcm[:, 0] is the sample before
+// the first one (a stream's later calls). mode: 0 whole signal, 1 stream in flight, 2 stream end.
+void featurize(at::Tensor pcm, OptT lens, at::Tensor offset, at::Tensor gain, at::Tensor basis, OptT mel_idx,
+               OptT mel_w, OptT dct, OptT lifter, int64_t kind, int64_t lead, int64_t mode, at::Tensor out,
+               at::Tensor frames) {
+  const int i16 = pcm_is_i16(pcm);
+  const int64_t B = pcm.size(0), S = pcm.size(1);
+  TORCH_CHECK(kind == 0 || kind == 1, "featurize: kind 0 (mfcc) or 1 (spectrogram)");
+  TORCH_CHECK((lead == 0 || lead == 1) && mode >= 0 && mode <= 2 && S >= lead && S < (1LL << 31), "featurize: lead / mode / S");
+  for (const at::Tensor* t : {&offset, &gain, &basis, &out, &frames}) need_gpu(*t, "featurize operand");
+  TORCH_CHECK(offset.scalar_type() == at::kFloat && offset.numel() == B && gain.scalar_type() == at::kFloat &&
+                  gain.numel() == B, "offset / gain must be fp32 [B]");
+  const int64_t L = kind == 0 ? 400 : 320, NCOL = kind == 0 ? 512 : 320;
+  TORCH_CHECK(basis.scalar_type() == at::kFloat && basis.numel() == L * NCOL, "featurize: basis must be fp32 [", L, ", ", NCOL, "]");
+  TORCH_CHECK(out.dim() == 3 && out.size(0) == B && out.size(2) == 161, "featurize: out must be [B, T_max, 161]");
+  TORCH_CHECK(frames.scalar_type() == at::kInt && frames.numel() == B, "frames must be int32 [B]");
+  DS2Feat a{};
+  a.pcm = pcm.data_ptr();
+  a.row_stride = S;
+  a.S = (int)S; a.lead = (int)lead; a.mode = (int)mode; a.B = (int)B; a.T_max = (int)out.size(1);
+  a.lens = feat_lens(lens, B);
+  a.offset = offset.data_ptr<float>();
+  a.gain = gain.data_ptr<float>();
+  a.basis = basis.data_ptr<float>();
+  if (kind == 0) {
+    a.mel_idx = ptr_or_null<const int>(mel_idx, "mel_idx");
+    a.mel_w = ptr_or_null<const float>(mel_w, "mel_w");
+    a.dct = ptr_or_null<const float>(dct, "dct");
+    a.lifter = ptr_or_null<const float>(lifter, "lifter");
+    TORCH_CHECK(a.mel_idx && a.mel_w && a.dct && a.lifter, "featurize: mfcc needs the mel, DCT and lifter tables");
+    TORCH_CHECK(mel_idx->scalar_type() == at::kInt && mel_idx->numel() == 322 * 2 && mel_w->scalar_type() == at::kFloat &&
+                    mel_w->numel() == 322 * 8 && dct->scalar_type() == at::kFloat && dct->numel() == 322 * 192 &&
+                    lifter->scalar_type() == at::kFloat && lifter->numel() == 161, "featurize: mfcc table shapes");
+  }
+  a.out = out.data_ptr();
+  a.frames = frames.data_ptr<int>();
+  check(ds2_featurize(&a, (int)kind, i16, is_bf16(out), cur_stream()), "featurize");
+}
+
 // --------------------------------------------------------------------------- summaries (csrc/stats.hip)
 void hist_stats(at::Tensor x, at::Tensor counts, at::Tensor part) {
   need_gpu(x, "x");
@@ -1679,6 +1766,10 @@ PYBIND11_MODULE(_C, m) {
         py::arg("label_lens"), py::arg("loss"), py::arg("G"), py::arg("ws"), py::arg("blank"), py::arg("zero_inf"),
         py::arg("mean") = py::none(), py::arg("counter") = py::none(), py::arg("first_bad") = py::none());
   m.def("fc_logits", &fc_logits);
+  m.def("audio_stats", &audio_stats, py::arg("pcm"), py::arg("lens"), py::arg("offset"), py::arg("gain"));
+  m.def("featurize", &featurize, py::arg("pcm"), py::arg("lens"), py::arg("offset"), py::arg("gain"),
+        py::arg("basis"), py::arg("mel_idx"), py::arg("mel_w"), py::arg("dct"), py::arg("lifter"), py::arg("kind"),
+        py::arg("lead"), py::arg("mode"), py::arg("out"), py::arg("frames"));
   m.def("hist_stats", &hist_stats);
   m.def("hist_nbucket", []() { return ds2_hist_nbucket(); });
   m.def("hist_blocks", [](int64_t n) { return ds2_hist_blocks(n); });

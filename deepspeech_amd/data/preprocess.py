@@ -2,6 +2,11 @@
 
   python -m deepspeech_amd.data.preprocess --audio_path ../data/LibriSpeech/audio \
          --out_dir ../data/LibriSpeech/processed [--features mfcc|spectrogram] [--tfrecords]
+         [--featurizer numpy|gpu]
+
+``--featurizer numpy`` (default) runs data/featurizer.py one file at a time; ``gpu`` batches
+about 64 utterances per call through the HIP featurizer (ops/featurize.py) and feeds the same
+sort / store / TFRecord code.
 
 For every partition directory under ``audio_path`` (train-clean-100, dev-clean, ...):
 read ``*.trans.txt`` transcripts, decode audio, compute features, map characters with the
@@ -73,13 +78,52 @@ def scan_partition(part_dir: str) -> List[Tuple[str, str]]:
     return items
 
 
-def process_partition(part_dir: str, out_prefix: str, features: str = "mfcc",
-                      tfrecord_dir: str = "", is_train: bool = False, min_bin: int = 20) -> Dict[str, int]:
+GPU_GROUP = 64        # utterances per AudioFeaturizer call of --featurizer gpu
+
+
+def _gpu_features(items: List[Tuple[str, str]], features: str) -> list:
+    """[(feats, labels, text)] in the order of ``items``, featurized on the GPU in groups of
+    GPU_GROUP files sorted by length (bounds the padding of a group's [B, S_max] upload)."""
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("--featurizer gpu needs a GPU (none is visible); use --featurizer numpy")
+    from ..ops.featurize import AudioFeaturizer
+    fz: Dict[int, AudioFeaturizer] = {}
     utts = []
-    for path, text in scan_partition(part_dir):
-        audio, sr = read_audio(path)
-        feats = compute_features(audio, sr, features)
-        utts.append((feats, encode_transcript(text), text))
+    for g0 in range(0, len(items), GPU_GROUP):
+        group = []
+        for path, text in items[g0:g0 + GPU_GROUP]:
+            audio, sr = read_audio(path)
+            group.append((audio, sr, text))
+        order = sorted(range(len(group)), key=lambda i: (group[i][1], len(group[i][0])))
+        done = {}
+        for sr in sorted({g[1] for g in group}):
+            idx = [i for i in order if group[i][1] == sr]
+            if sr not in fz:
+                fz[sr] = AudioFeaturizer(features, sample_rate=sr, device="cuda", normalize="utterance")
+            # float32 PCM on the device: exact for 16-bit audio
+            feats, frames = fz[sr]([group[i][0].astype(np.float32) for i in idx])
+            feats, frames = feats.cpu().numpy(), frames.cpu().tolist()
+            for k, i in enumerate(idx):
+                done[i] = np.ascontiguousarray(feats[k, :frames[k]])
+        for i, (_, _, text) in enumerate(group):
+            utts.append((done[i], encode_transcript(text), text))
+    return utts
+
+
+def process_partition(part_dir: str, out_prefix: str, features: str = "mfcc",
+                      tfrecord_dir: str = "", is_train: bool = False, min_bin: int = 20,
+                      featurizer: str = "numpy") -> Dict[str, int]:
+    if featurizer not in ("numpy", "gpu"):
+        raise ValueError("featurizer must be 'numpy' or 'gpu', not %r" % (featurizer,))
+    utts = []
+    if featurizer == "gpu":
+        utts = _gpu_features(scan_partition(part_dir), features)
+    else:
+        for path, text in scan_partition(part_dir):
+            audio, sr = read_audio(path)
+            feats = compute_features(audio, sr, features)
+            utts.append((feats, encode_transcript(text), text))
     utts.sort(key=lambda u: u[0].shape[0])                 # SortaGrad order
     w = StoreWriter(out_prefix, utts[0][0].shape[1] if utts else 161)
     for feats, lab, text in utts:
@@ -110,13 +154,16 @@ def main(argv=None):
     ap.add_argument("--out_dir", default="../data/LibriSpeech/processed")
     ap.add_argument("--features", default="mfcc", choices=["mfcc", "spectrogram"])
     ap.add_argument("--tfrecords", action="store_true")
+    ap.add_argument("--featurizer", default="numpy", choices=["numpy", "gpu"],
+                    help="numpy: data/featurizer.py, one file at a time; gpu: batched HIP kernels (ops/featurize.py)")
     a = ap.parse_args(argv)
     for part in sorted(glob.glob(os.path.join(a.audio_path, "*"))):
         if not os.path.isdir(part):
             continue
         name = os.path.basename(part)
         stats = process_partition(part, os.path.join(a.out_dir, name), a.features,
-                                  a.out_dir if a.tfrecords else "", is_train=name.startswith("train"))
+                                  a.out_dir if a.tfrecords else "", is_train=name.startswith("train"),
+                                  featurizer=a.featurizer)
         print(name, stats)
 
 

@@ -44,9 +44,15 @@ def frames_out(T: int) -> int:
 
 class StreamingRecognizer:
     def __init__(self, model: DeepSpeech2, decoder: str = "greedy", beam_width: int = 16, batch: int = 1,
-                 graphs: Optional[bool] = None):
+                 graphs: Optional[bool] = None, features: str = "mfcc", audio_gain: Optional[float] = None):
         if model.bidirectional:
             raise ValueError("streaming needs a unidirectional model (rnn_type='uni-dir')")
+        # accept_audio(): PCM is featurized on the model's device (ops/featurize.py) with a fixed
+        # gain (None: 1/32768 for int16 PCM, 1 for float); the featurizer is built on first use
+        self.features = features
+        self.audio_gain = audio_gain
+        self._featurizer = None
+        self._audio = None
         self.model = model.eval()
         self.decoder = decoder
         self.beam_width = beam_width
@@ -85,6 +91,26 @@ class StreamingRecognizer:
         self.last_sym = [-1] * self.B
         self.greedy: List[List[int]] = [[] for _ in range(self.B)]
         self.compute_s = 0.0
+        self._audio = None if self._featurizer is None else self._featurizer.stream(self.B)
+
+    @torch.no_grad()
+    def accept_audio(self, pcm, final: bool = False) -> List[List[int]]:
+        """Feed [B, S_c] PCM samples (int16 or float, 16 kHz); the feature frames they complete go
+        through accept(). ``final=True`` also emits the zero-padded last frame. Returns the newly
+        decoded (greedy) labels per stream."""
+        t0 = time.perf_counter()
+        if self._featurizer is None:
+            from .ops.featurize import AudioFeaturizer
+            self._featurizer = AudioFeaturizer(self.features, device=self.dev, normalize="fixed",
+                                               gain=self.audio_gain)
+            self._audio = self._featurizer.stream(self.B)
+        feats = self._audio.push(pcm, final=final)
+        # no sync here: the kernels run ahead of accept()'s on the same stream, so their GPU time
+        # falls inside accept()'s timed section; this one covers the host side of the push
+        self.compute_s += time.perf_counter() - t0
+        if feats.shape[1] == 0:
+            return [[] for _ in range(self.B)]
+        return self.accept(feats)
 
     @torch.no_grad()
     def accept(self, chunk: torch.Tensor) -> List[List[int]]:
@@ -212,10 +238,21 @@ class StreamingRecognizer:
 
 
 def rtf(model: DeepSpeech2, seconds: float = 10.0, chunk_s: float = 1.0, batch: int = 1,
-        decoder: str = "greedy", beam_width: int = 16, seed: int = 0):
+        decoder: str = "greedy", beam_width: int = 16, seed: int = 0, audio: bool = False):
     """Real-time factor of streaming synthetic audio: compute time / audio time (per stream;
-    ``batch`` streams are processed together). Returns (rtf, transcripts)."""
+    ``batch`` streams are processed together). Returns (rtf, transcripts). ``audio=True`` streams
+    synthetic int16 PCM through accept_audio() (featurization included in the compute time)
+    instead of ready-made feature frames."""
     g = torch.Generator().manual_seed(seed)
+    if audio:
+        n = int(round(seconds * 16000))
+        pcm = (torch.randn(batch, n, generator=g) * 3000.0).clamp_(-32768, 32767).to(torch.int16)
+        rec = StreamingRecognizer(model, decoder=decoder, beam_width=beam_width, batch=batch)
+        step = max(1, int(round(chunk_s * 16000)))
+        for s in range(0, n, step):
+            rec.accept_audio(pcm[:, s:s + step], final=s + step >= n)
+        res = rec.finish()
+        return rec.compute_s / seconds, res
     T = int(round(seconds * 100))
     feats = torch.randn(batch, T, model.freq_bins, generator=g)
     rec = StreamingRecognizer(model, decoder=decoder, beam_width=beam_width, batch=batch)
