@@ -111,7 +111,8 @@ def build(force: bool = False, verbose: bool = False, jobs: int = 0, defines=(),
     jobs = jobs or min(8, os.cpu_count() or 4)
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
         futs = [ex.submit(_compile, s, BUILD, hip_flags, _local_deps(s)) for s in hip_srcs]
-        futs.append(ex.submit(_compile, os.path.join(CSRC, "bindings.cpp"), BUILD, bind_flags, []))
+        bind_src = os.path.join(CSRC, "bindings.cpp")
+        futs.append(ex.submit(_compile, bind_src, BUILD, bind_flags, _local_deps(bind_src)))
         objs = [f.result() for f in futs]
     out = os.path.join(PKG, "_C" + EXT)
     stamp = os.path.join(BUILD, "_C.link")

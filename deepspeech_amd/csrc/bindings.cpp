@@ -12,252 +12,7 @@
 #include <string>
 #include <vector>
 
-extern "C" {
-struct DS2RnnFwd {
-  int T, N, NP, H, S, BG, steps, gstride, ndir, cell, nw, mt, persistent;
-  const int* lens;
-  const void* gx;
-  const void* U[2];
-  const float* bh[2];
-  void* y[2];
-  void* hx[2];
-  float* hsave[2];
-  float* gates[2];
-  unsigned* flags;
-  unsigned* err;
-  long long timeout;
-  unsigned long long* stamps;
-};
-struct DS2RnnBwd {
-  int T, N, NP, H, S, BG, steps, gstride, ndir, cell, nw, mt, persistent;
-  const int* lens;
-  const void* dy;
-  const void* U[2];
-  const float* hsave[2];
-  const float* gates[2];
-  void* dgh[2];
-  void* dgx;
-  float* carry[2];
-  float* dbx_part[2];
-  float* dbh_part[2];
-  float dgx_scale;
-  unsigned* flags;
-  unsigned* err;
-  long long timeout;
-  unsigned long long* stamps;
-};
-int ds2_rnn_fwd(const DS2RnnFwd* d, hipStream_t st);
-int ds2_rnn_bwd(const DS2RnnBwd* d, hipStream_t st);
-int ds2_rnn_fwd_stamps(const DS2RnnFwd* d, hipStream_t st);
-int ds2_rnn_bwd_stamps(const DS2RnnBwd* d, hipStream_t st);
-int ds2_rnn_kpw(int H, int G, int nw, int fwd);
-struct DS2RnnX {
-  int T, N, NP, H, BG, R, steps, gstride, ndir, cell, mt, xcd_map, knobs;
-  const int* lens;
-  const void* gx;
-  const void* U[2];
-  const float* bh[2];
-  void* y[2];
-  void* ex[2];
-  float* hsave[2];
-  float* gates[2];
-  void* dgx;
-  float* dbx_part[2];
-  float* dbh_part[2];
-  float dgx_scale;
-  unsigned* census;
-  unsigned* err;
-  long long timeout;
-  unsigned long long* stamps;
-  void* ring[2];
-  void* ysum;
-};
-int ds2_rnnx_fwd(const DS2RnnX* d, hipStream_t st);
-struct DS2RnnF8 {
-  int T, N, NP, H, BG, R, steps, gstride, ndir, xcd_map;
-  const int* lens;
-  const void* gx;
-  const void* U8[2];
-  const int* uexp;
-  const float* bh[2];
-  void* y[2];
-  void* hq[2];
-  void* hx[2];
-  float* hsave[2];
-  float* gates[2];
-  unsigned* census;
-  unsigned* err;
-  long long timeout;
-};
-int ds2_rnnf8_supported(int H, int N, int ndir);
-int ds2_rnnf8_fwd(const DS2RnnF8* d, hipStream_t st);
-int ds2_fp8_quant_pow2(const void* x, long long n, void* q, int* uexp, unsigned* amax, hipStream_t st);
-struct DS2RnnF8B {
-  int T, N, NP, H, BG, R, steps, gstride, ndir, xcd_map;
-  const int* lens;
-  const void* dy;
-  const void* U8T[2];
-  const int* uexp;
-  const float* hsave[2];
-  const float* gates[2];
-  void* dgh[2];
-  void* dgx;
-  void* ring[2];
-  float* dbx_part[2];
-  float* dbh_part[2];
-  float dgx_scale;
-  unsigned* census;
-  unsigned* err;
-  long long timeout;
-};
-int ds2_rnnf8_bwd_supported(int H, int N, int ndir);
-long long ds2_rnnf8_ring_words(int H, int BG, int R);
-int ds2_rnnf8_bwd(const DS2RnnF8B* d, hipStream_t st);
-int ds2_fp8_quant_u(int ndir, const void* const* x, int rows, int cols, void* const* q, void* const* qt, int* uexp,
-                    float* part, hipStream_t st);
-int ds2_fp8_quant_pow2_t(const void* x, int rows, int cols, void* q, int* uexp, unsigned* amax, hipStream_t st);
-int ds2_rnnx_fwd_fuses_sum(int H, int cell, int mt, int ndir, int knobs);
-int ds2_rnnx_fwd_family(int H, int cell, int mt, int knobs);
-int ds2_rnnx_bwd_family(int H, int cell, int mt, int R);
-int ds2_rnnx_bwd_rs(const DS2RnnX* d, hipStream_t st);
-long long ds2_rnnx_ring_floats(int H, int BG, int R);
-int ds2_rnnx_grid(int H, int cell, int ngroups, int xcd_map);
-int ds2_rnnx_kb(int H, int G, int fwd);
-size_t ds2_rnnx_smem(int H, int G, int mt, int fwd);
-int ds2_ctc_fused(const void* logits, int logits_bf16, const int* lens, const int* labels, const int* label_lens,
-                  float* loss, void* grad, float* ws, int T, int N, int K, int Lmax, int blank, int zero_inf,
-                  hipStream_t st);
-long long ds2_ctc_ws_floats(int T, int N, int Lmax);
-int ds2_bn_stats(const void* y, int y_bf16, int N, int C, int T, int F, float* part, int nb, float eps, float* mean,
-                 float* invstd, float* run_mean, float* run_var, float momentum, hipStream_t st);
-int ds2_bn_chunks(int N, int T, int F);
-int ds2_bn_apply(const void* y, int y_bf16, const float* mean, const float* invstd, const float* gamma,
-                 const float* beta, void* out, int out_bf16, int N, int C, int T, int F, int layout, hipStream_t st);
-int ds2_bn_bwd(const void* dout, int dout_bf16, const void* y, int y_bf16, const float* mean, const float* invstd,
-               const float* gamma, const float* beta, float* part, int nb, float* dgamma, float* dbeta, void* dy,
-               int dy_bf16, int N, int C, int T, int F, int layout, hipStream_t st);
-int ds2_adam_ema(float* p, const float* g, float* m, float* v, float* ema, void* p16, long long n, float lr_t,
-                 float b1, float b2, float eps, float gscale, float ema_keep, const int* skip, int max_grid,
-                 const float* hyper, int lds_reserve, hipStream_t st);
-int ds2_grad_norm_blocks(long long n);
-int ds2_grad_norm(const float* g, long long n, float gscale, float* part, int nblocks, int* bad, hipStream_t st);
-int ds2_cast_bf16(const float* x, void* y, long long n, hipStream_t st);
-int ds2_fp8_quant_blocks(long long na, long long nb_el);
-int ds2_gemm8(const void* A, const void* B, void* C, const void* bias, const float* alpha_dev,
-              const float* alpha_dev2, int M, int N, int K, int lda, int ldb, int ldc, int fp8, int a_col, int b_col,
-              int epi, float alpha, int batch, long long sA, long long sB, long long sC, int S, float* ws,
-              unsigned* cnt, int cus, const struct DS2Fill* fill, int ext_red, hipStream_t st);
-int ds2_gemm8_splits(int K, int fp8, int S);
-struct DS2Fill {       // csrc/gemm8.hip: regions the launch's idle workgroups initialise
-  int n;
-  unsigned* ptr[8];
-  unsigned long long words[8];
-  unsigned pattern[8];
-};
-struct DS2G8Opt {      // csrc/gemm8.hip: Adam + EMA in the grouped GEMM's epilogue
-  float* p;
-  float* m;
-  float* v;
-  float* ema;
-  unsigned short* p16;
-  const float* gbase;
-  float lr_t, b1, b2, eps, gscale, keep;
-  int on, store_g;
-};
-int ds2_gemm8_group(int np, const void* const* A, const void* const* B, void* const* C, float* const* ws,
-                    unsigned* const* cnt, const int* dims, int a_col, int b_col, int cus, const DS2G8Opt* opt,
-                    hipStream_t st);
-int ds2_adam_ema_ranges(float* p, const float* g, float* m, float* v, float* ema, void* p16, const long long* lohi,
-                        int nr, float lr_t, float b1, float b2, float eps, float gscale, float ema_keep,
-                        const float* hyper, hipStream_t st);
-int ds2_fp8_quant2(const void* a, long long rows_a, const void* b, long long rows_b, int K, int Kp, float alpha,
-                   void* a8, void* b8, float* part, float* scales, const void* a2, void* asum, hipStream_t st);
-int ds2_transpose_bf16(const void* in, void* out, int R, int C, int ldi, int ldo, hipStream_t st);
-int ds2_prep_inputs(const float* x, void* y, long long n, const int* lens_in, int* lens_out, int nl,
-                    hipStream_t st);
-int ds2_multi_copy(int n, void* const* dst, const void* const* src, const unsigned long long* rows,
-                   const unsigned* src_row, const unsigned* dst_row, const unsigned* src_pitch,
-                   const unsigned* dst_pitch, float* sdst, const float* svals, int ns, hipStream_t st);
-int ds2_multi_fill(int n, void* const* ptrs, const unsigned long long* bytes, const unsigned* patterns,
-                   hipStream_t st);
-int ds2_wait_resident(const unsigned* word, long long timeout, hipStream_t st);
-int ds2_col_sum(int n, const float* const* in, float* const* out, const int* R, const int* B, const int* C,
-                const int* acc, hipStream_t st);
-int ds2_fc_bias_grad(const void* G, int M, int ldg, int K, const float* scale, float alpha, float* out, int acc,
-                     hipStream_t st);
-int ds2_ctc_beam(const float* lp, const int* frames, int T, int B, int K, int W, int blank, float prune, int* node,
-                 int* last, int* parent, float* pb, float* pnb, int* nbeam, void* nodes, int* nnodes, int cap,
-                 unsigned* err, hipStream_t st);
-int ds2_ctc_beam_backtrack(const void* nodes, int cap, const int* node, const int* nbeam, const float* pb,
-                           const float* pnb, int B, int W, int* out, int* out_len, float* score, int Lcap,
-                           hipStream_t st);
-int ds2_ctc_greedy(const void* logits, int bf16, const int* lens, int T, int N, int K, int blank,
-                   int* labels, int* counts, float* score, hipStream_t st);
-size_t ds2_conv2_fwd_smem(int F1);
-size_t ds2_conv2_dgrad_smem(int F2);
-size_t ds2_conv2_wgrad_smem(int F1);
-long long ds2_conv2_wgrad_part_floats(int grid);
-long long ds2_conv1_wgrad_part_floats(int grid);
-int ds2_conv1_fwd_grid(int N, int T1);
-int ds2_conv2_fwd(const void* x, const void* w, const float* bias, void* y, float* part, int grid, int N, int T1,
-                  int F1, int T2, int F2, long long* trace, hipStream_t st);
-struct DS2Conv2DgradBn {  // csrc/conv_frontend.hip: conv1's BN-backward sums in the dgrad epilogue
-  const void* y1;
-  const float *mean, *invstd, *gamma, *beta;
-  float* part;
-};
-int ds2_conv2_dgrad(const void* dy, const void* w, void* dx, int grid, int N, int T1, int F1, int T2, int F2,
-                    const DS2Conv2DgradBn* bn, long long* trace, hipStream_t st);
-int ds2_conv2_wgrad(const void* dy, const void* x, float* part, int grid, float* dw, int N, int T1, int F1, int T2,
-                    int F2, hipStream_t st);
-int ds2_conv1_fwd(const void* x, const void* w, const float* bias, void* y, float* part, int N, int T, int F0,
-                  int T1, int F1, hipStream_t st);
-struct DS2Conv1WgradBn {  // csrc/conv_frontend.hip: conv1's BN-backward apply in the wgrad staging
-  const void *dz, *y1;
-  const float *mean, *invstd, *gamma, *beta, *dbeta, *dgamma;
-};
-int ds2_conv1_wgrad(const void* dy, const void* x, float* part, int grid, float* dw, int N, int T, int F0, int T1,
-                    int F1, const DS2Conv1WgradBn* bn, hipStream_t st);
-int ds2_bn_cl_finalize(const float* part, int nb, double M, float eps, float* mean, float* invstd, float* run_mean,
-                       float* run_var, float momentum, hipStream_t st);
-int ds2_bn_cl_apply(const void* y, const float* mean, const float* invstd, const float* gamma, const float* beta,
-                    void* out, int N, int T, int F, int tmaj, hipStream_t st);
-int ds2_bn_cl_bwd(const void* dz, const void* y, const float* mean, const float* invstd, const float* gamma,
-                  const float* beta, float* part, int nb, float* dgamma, float* dbeta, void* dy, int N, int T, int F,
-                  int tmaj, int part_ready, hipStream_t st);
-int ds2_gemm(const void* A, const void* B, void* C, const void* bias, const float* alpha_dev, int M, int N, int K,
-             int lda, int ldb, int ldc, int Ml, int Nl, int Kl, int a_col, int b_col, int epi, float alpha, int batch,
-             long long sA, long long sB, long long sC, int cfg, const DS2Fill* fill, hipStream_t st);
-int ds2_gemm_tile(int cfg, int* bm, int* bn);
-int ds2_head_ctc(const void* h, const void* W, const void* bias, const int* lens, const int* labels,
-                 const int* label_lens, float* loss, void* G, float* ws, int T, int N, int H, int K, int Lmax,
-                 int blank, int zero_inf, float* mean, int* counter, int* first_bad, hipStream_t st);
-int ds2_hist_nbucket();
-int ds2_hist_blocks(long long n);
-int ds2_hist_stats(const void* x, int bf16, long long n, unsigned* counts, float* part, int blocks, hipStream_t st);
-int ds2_nonfinite_watch(const float* loss, int* counter, int* first_bad, hipStream_t st);
-int ds2_spin(long long ticks, int blocks, int threads, int lds_bytes, int* done, hipStream_t st);
-int ds2_fc_logits(const void* h, const void* W, const void* bias, void* logits, int out_bf16, int M, int H, int K,
-                  hipStream_t st);
-struct DS2Feat {          // csrc/featurize.hip
-  const void* pcm;
-  long long row_stride;
-  int S, lead, mode, B, T_max;
-  const int* lens;
-  const float* offset;
-  const float* gain;
-  const float* basis;
-  const int* mel_idx;
-  const float* mel_w;
-  const float* dct;
-  const float* lifter;
-  void* out;
-  int* frames;
-};
-int ds2_audio_stats(const void* pcm, int in_i16, long long row_stride, int S, int B, const int* lens, float* offset,
-                    float* gain, hipStream_t st);
-int ds2_featurize(const DS2Feat* a, int kind, int in_i16, int out_bf16, hipStream_t st);
-}
+#include "api.h"
 
 namespace {
 
@@ -295,8 +50,6 @@ bool event_query(int64_t e) { return hipEventQuery((hipEvent_t)(intptr_t)e) == h
 // The next kernel launched through ds2_launch (the GEMMs, the BPTT, multi_fill) completes event
 // e itself (hipExtLaunchKernel stop event) instead of a marker packet recorded behind it.
 // disarm_stop_event: True if no launch took it (the op ran elsewhere: record it the usual way).
-extern "C" hipEvent_t ds2_take_stop_event();
-extern "C" void ds2_arm_stop_event(hipEvent_t e);
 void arm_stop_event(int64_t e) { ds2_arm_stop_event((hipEvent_t)(intptr_t)e); }
 bool disarm_stop_event() { return ds2_take_stop_event() != nullptr; }
 
@@ -687,13 +440,9 @@ void rnnx_bwd(at::Tensor dy, at::Tensor lens, at::Tensor U_f, OptT U_b, at::Tens
   check(ds2_rnnx_bwd_rs(&d, cur_stream()), "rnnx_bwd_rs");
 }
 
-py::dict rnnx_info(int64_t H, int64_t G, int64_t mt, int64_t ngroups, int64_t xcd_map) {
+py::dict rnnx_info(int64_t H, int64_t G, int64_t ngroups, int64_t xcd_map) {
   py::dict d;
   d["grid"] = ds2_rnnx_grid((int)H, G == 3 ? 1 : 0, (int)ngroups, (int)xcd_map);
-  d["kb_fwd"] = ds2_rnnx_kb((int)H, (int)G, 1);
-  d["kb_bwd"] = ds2_rnnx_kb((int)H, (int)G, 0);
-  d["smem_fwd"] = (int64_t)ds2_rnnx_smem((int)H, (int)G, (int)mt, 1);
-  d["smem_bwd"] = (int64_t)ds2_rnnx_smem((int)H, (int)G, (int)mt, 0);
   return d;
 }
 
@@ -1321,13 +1070,9 @@ void gemm8(at::Tensor A, at::Tensor B, at::Tensor C, OptT bias, int64_t epi, dou
 // their tiles): C[i] (fp32, epi[i] 1 store / 2 accumulate) = A[i] B[i]^T, split-K S[i] through
 // consecutive ranges of one workspace ws (S[i] * M * N floats each) and one zeroed counter
 // buffer cnt (tiles each).
-// opt: [p, m, v, ema or None, p16 or None, grad arena] fp32 arena buffers and optf = [lr_t, b1,
-// b2, eps, gscale, keep]: Adam + EMA of the members' elements in the epilogue (members: epi 1
-// views of the gradient arena); store_g also writes the gradient.
 void gemm8_group(std::vector<at::Tensor> A, std::vector<at::Tensor> B, std::vector<at::Tensor> C,
                  std::vector<int64_t> epi, std::vector<int64_t> splits, bool a_col, bool b_col, OptT ws, OptT cnt,
-                 int64_t max_grid, std::vector<c10::optional<at::Tensor>> opt, std::vector<double> optf,
-                 bool store_g) {
+                 int64_t max_grid) {
   const size_t np = A.size();
   TORCH_CHECK(np >= 1 && np <= 24 && B.size() == np && C.size() == np && epi.size() == np && splits.size() == np,
               "gemm8_group: 1..24 members, one A, B, C, epi, splits each");
@@ -1373,43 +1118,9 @@ void gemm8_group(std::vector<at::Tensor> A, std::vector<at::Tensor> B, std::vect
     d[3] = (int)a.stride(0); d[4] = (int)b.stride(0); d[5] = (int)c.stride(0);
     d[6] = (int)epi[i]; d[7] = S;
   }
-  DS2G8Opt o{};
-  if (!opt.empty()) {
-    TORCH_CHECK(opt.size() == 6 && optf.size() == 6, "gemm8_group: opt = [p, m, v, ema, p16, grad], 6 constants");
-    auto f32 = [&](int i, bool need) -> float* {
-      const auto& t = opt[i];
-      if (!t.has_value() || !t->defined()) {
-        TORCH_CHECK(!need, "gemm8_group: optimizer buffer ", i, " required");
-        return nullptr;
-      }
-      TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous(), "gemm8_group: fp32 arena ", i);
-      return t->data_ptr<float>();
-    };
-    o.p = f32(0, true); o.m = f32(1, true); o.v = f32(2, true); o.ema = f32(3, false);
-    const float* g = f32(5, true);
-    const int64_t n = opt[5]->numel();
-    for (int i : {0, 1, 2, 3})
-      TORCH_CHECK(!opt[i].has_value() || !opt[i]->defined() || opt[i]->numel() == n, "gemm8_group: arena sizes");
-    if (opt[4].has_value() && opt[4]->defined()) {
-      TORCH_CHECK(opt[4]->scalar_type() == at::kBFloat16 && opt[4]->numel() == n && opt[4]->is_contiguous(),
-                  "gemm8_group: bf16 shadow");
-      o.p16 = reinterpret_cast<unsigned short*>(opt[4]->data_ptr());
-    }
-    for (size_t i = 0; i < np; ++i) {
-      const int64_t e0 = C[i].data_ptr<float>() - g;
-      TORCH_CHECK(e0 >= 0 && e0 % 4 == 0 && C[i].stride(0) % 4 == 0 && epi[i] == 1 &&
-                      e0 + (C[i].size(0) - 1) * C[i].stride(0) + C[i].size(1) <= n,
-                  "gemm8_group: fused-optimizer member ", i, " must be an aligned first-write view of the arena");
-    }
-    o.gbase = g;
-    o.lr_t = (float)optf[0]; o.b1 = (float)optf[1]; o.b2 = (float)optf[2]; o.eps = (float)optf[3];
-    o.gscale = (float)optf[4]; o.keep = (float)optf[5];
-    o.on = 1;
-    o.store_g = store_g ? 1 : 0;
-  }
   check(ds2_gemm8_group((int)np, pa.data(), pb.data(), pc.data(), pw.data(), pn.data(), dims.data(), a_col ? 1 : 0,
                         b_col ? 1 : 0, max_grid > 0 ? (int)std::min<int64_t>(max_grid, dev_cus()) : dev_cus(),
-                        o.on ? &o : nullptr, cur_stream()),
+                        cur_stream()),
         "gemm8_group");
 }
 
@@ -1717,9 +1428,7 @@ PYBIND11_MODULE(_C, m) {
         py::arg("cnt") = py::none(), py::arg("max_grid") = 0, py::arg("fill") = std::vector<at::Tensor>{},
         py::arg("fill_pat") = std::vector<int64_t>{}, py::arg("ext_red") = false);
   m.def("gemm8_group", &gemm8_group, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("epi"), py::arg("splits"),
-        py::arg("a_col"), py::arg("b_col"), py::arg("ws"), py::arg("cnt"), py::arg("max_grid"),
-        py::arg("opt") = std::vector<c10::optional<at::Tensor>>{}, py::arg("optf") = std::vector<double>{},
-        py::arg("store_g") = false);
+        py::arg("a_col"), py::arg("b_col"), py::arg("ws"), py::arg("cnt"), py::arg("max_grid"));
   m.def("gemm8_splits", [](int64_t K, bool fp8, int64_t S) { return ds2_gemm8_splits((int)K, fp8 ? 1 : 0, (int)S); });
   m.def("multi_fill", &multi_fill);
   m.def("col_sum", &col_sum);

@@ -4,6 +4,8 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include "api.h"
+
 namespace ds2 {
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8;   // MFMA 16x16x32 A/B fragment
@@ -98,9 +100,8 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 
 // One element of TF's Adam (epsilon-hat form) and of the weight EMA, every rounding spelled out
 // (explicit fma / _rn products, nothing left to the compiler's contraction choice), so every
-// kernel that applies the update — the streaming optimizer (optim.hip) and the fused epilogue
-// of the grouped weight-gradient GEMM (gemm8.hip) — rounds identically: the result of an
-// element does not depend on which kernel or which launch split updated it.
+// kernel of the streaming optimizer (optim.hip) rounds identically: the result of an element
+// does not depend on which kernel or which launch split updated it.
 __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, float lr_t, float b1, float b2,
                                       float eps, float gscale) {
   const float gj = __fmul_rn(g, gscale);
@@ -123,20 +124,8 @@ __device__ __forceinline__ float wave_max(float v) {
 
 }  // namespace ds2
 
-// Buffers the NEXT kernel of a stream needs initialised (a recurrence's h0 slots, sentinel-
-// filled exchange slots, census words, bias partials): written by a persistent GEMM launch's
-// lighter workgroups (one work unit fewer than the busiest) after their last unit, while the
-// others finish theirs, instead of by a separate multi_fill launch on the critical path
-// (csrc/fill.hip semantics: region r = words[r] 32-bit words of pattern[r]).
-struct DS2Fill {
-  int n;
-  unsigned* ptr[8];
-  unsigned long long words[8];
-  unsigned pattern[8];
-};
-
-// This workgroup's share of a DS2Fill in a persistent grid over `total` work units where XCD x
-// walks [x * tx, (x + 1) * tx) and its workgroup l (blockIdx = 8 l + x, per = gridDim / 8 of
+// This workgroup's share of a DS2Fill (api.h) in a persistent grid over `total` work units where
+// XCD x walks [x * tx, (x + 1) * tx) and its workgroup l (blockIdx = 8 l + x, per = gridDim / 8 of
 // them) owns units l, l + per, ...: a workgroup is light when it owns fewer than
 // ceil(tx / per), and the light ones (all of them when none is) split the regions' 16-B chunks
 // in (XCD, l) order. nthr: threads per workgroup.
@@ -170,13 +159,10 @@ __device__ inline void fill_idle(const DS2Fill& f, int total, int tx, int nthr) 
 }
 
 // Completion event armed for the next launch made through ds2_launch (hipExtLaunchKernel's stop
-// event; fill.hip ds2_arm_stop_event / ds2_take_stop_event): another stream can wait for that
-// kernel without a marker packet in this kernel's queue, each of which holds the queue ~6 us
+// event; fill.hip ds2_arm_stop_event / ds2_take_stop_event, declared in api.h): another stream
+// can wait for that kernel without a marker packet in this kernel's queue, each of which holds the queue ~6 us
 // between two kernels (tools/probe_event_gap.py). The host launchers whose kernel is the last
 // of an op take the event themselves and hand it to that launch.
-extern "C" hipEvent_t ds2_take_stop_event();
-extern "C" void ds2_arm_stop_event(hipEvent_t e);
-
 template <typename F, typename... Args>
 inline void ds2_launch(F kern, dim3 grid, dim3 block, unsigned lds, hipStream_t st, Args... args) {
   hipEvent_t e = ds2_take_stop_event();

@@ -41,19 +41,6 @@
 
 using namespace ds2;
 
-// optional BatchNorm-backward apply fused into conv1's weight-gradient staging (bindings.cpp)
-struct DS2Conv1WgradBn {
-  const void *dz, *y1;                             // bf16 [N][T1][F1][32]
-  const float *mean, *invstd, *gamma, *beta, *dbeta, *dgamma;
-};
-
-// optional BatchNorm-backward sums fused into the conv2 data-gradient epilogue (bindings.cpp)
-struct DS2Conv2DgradBn {
-  const void* y1;                                  // conv1 output [N][T1][F1][32] bf16
-  const float *mean, *invstd, *gamma, *beta;       // conv1 BN batch statistics and affine
-  float* part;                                     // [grid][32][2]
-};
-
 namespace {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;

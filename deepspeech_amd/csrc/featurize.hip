@@ -27,24 +27,6 @@
 // batch or the chunking of a stream. No host synchronisation, so a call can be graph-captured.
 #include "common.h"
 
-extern "C" {
-struct DS2Feat {
-  const void* pcm;        // [B, row_stride] samples; logical sample n of row b is pcm[b][lead + n]
-  long long row_stride;
-  int S, lead, mode, B, T_max;
-  const int* lens;        // [B] valid logical samples, or null (= S - lead)
-  const float* offset;    // [B]
-  const float* gain;      // [B]
-  const float* basis;     // [L, 2 * NH]
-  const int* mel_idx;     // [322, 2] (first bin, taps)           (mfcc)
-  const float* mel_w;     // [322, 8]                             (mfcc)
-  const float* dct;       // [322, 192], columns >= 161 zero      (mfcc)
-  const float* lifter;    // [161]                                (mfcc)
-  void* out;              // [B, T_max, 161]
-  int* frames;            // [B]
-};
-}
-
 namespace {
 
 using namespace ds2;

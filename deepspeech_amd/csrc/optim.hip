@@ -128,9 +128,8 @@ __global__ __launch_bounds__(OPT_THREADS) void adam_ema_chunk_kernel(
   }
 }
 
-// The same update over a list of arena ranges in ONE launch (the elements of a step that the
-// grouped weight-gradient GEMM's fused epilogue did not update: FC head, biases, padding):
-// thread i takes float4 group i of the ranges' concatenation. Ranges start and end on
+// The same update over a list of disjoint arena ranges in ONE launch (the elements between
+// the ranges stay untouched): thread i takes float4 group i of the ranges' concatenation. Ranges start and end on
 // float4 boundaries (host-checked).
 constexpr int ADAM_MAXR = 64;
 struct AdamRanges {

@@ -1228,23 +1228,6 @@ __global__ __launch_bounds__(256) void quant_u_kernel(const bf16_t* __restrict__
 
 extern "C" {
 
-struct DS2RnnF8 {
-  int T, N, NP, H, BG, R, steps, gstride, ndir, xcd_map;
-  const int* lens;
-  const void* gx;
-  const void* U8[2];
-  const int* uexp;
-  const float* bh[2];
-  void* y[2];
-  void* hq[2];
-  void* hx[2];
-  float* hsave[2];
-  float* gates[2];
-  unsigned* census;
-  unsigned* err;
-  long long timeout;
-};
-
 // k-steps of 128 per wave (K half) and how many of them live in LDS, for H
 static int f8_kb(int H) { return H / 256; }
 static int f8_kl(int kb) { return kb > 3 ? kb - 3 : 0; }
@@ -1296,25 +1279,6 @@ int ds2_rnnf8_fwd(const DS2RnnF8* d, hipStream_t st) {
   }
   return (int)hipGetLastError();
 }
-
-struct DS2RnnF8B {
-  int T, N, NP, H, BG, R, steps, gstride, ndir, xcd_map;
-  const int* lens;
-  const void* dy;
-  const void* U8T[2];
-  const int* uexp;
-  const float* hsave[2];
-  const float* gates[2];
-  void* dgh[2];
-  void* dgx;
-  void* ring[2];
-  float* dbx_part[2];
-  float* dbh_part[2];
-  float dgx_scale;
-  unsigned* census;
-  unsigned* err;
-  long long timeout;
-};
 
 // fp8 BPTT geometry: H = 256 k, k = 1..5 (P = H/64 <= 20 workgroups per group), R <= 8
 int ds2_rnnf8_bwd_supported(int H, int N, int ndir) {

@@ -650,42 +650,6 @@ static int dispatch_nw_mt(int nw, int mt, F4 f4, F8 f8) {
 
 extern "C" {
 
-// Python-visible descriptors (flat, fixed-layout structs filled by the bindings).
-struct DS2RnnFwd {
-  int T, N, NP, H, S, BG, steps, gstride, ndir, cell, nw, mt, persistent;
-  const int* lens;
-  const void* gx;
-  const void* U[2];
-  const float* bh[2];
-  void* y[2];
-  void* hx[2];
-  float* hsave[2];
-  float* gates[2];
-  unsigned* flags;
-  unsigned* err;
-  long long timeout;
-  unsigned long long* stamps;
-};
-
-struct DS2RnnBwd {
-  int T, N, NP, H, S, BG, steps, gstride, ndir, cell, nw, mt, persistent;
-  const int* lens;
-  const void* dy;
-  const void* U[2];
-  const float* hsave[2];
-  const float* gates[2];
-  void* dgh[2];
-  void* dgx;
-  float* carry[2];
-  float* dbx_part[2];
-  float* dbh_part[2];
-  float dgx_scale;
-  unsigned* flags;
-  unsigned* err;
-  long long timeout;
-  unsigned long long* stamps;
-};
-
 int DS2_EXPORT(ds2_rnn_kpw)(int H, int G, int nw, int fwd) {
   const int ks = fwd ? H / 32 : G * H / 32;
   return pick_kpw((ks + nw - 1) / nw);

@@ -2440,11 +2440,11 @@ __global__ __launch_bounds__(NTH) void rnnw_bwd_kernel(XBwdRS a) {
 }
 
 template <int CELL, int MT>
-static int launch_fwd(const XFwd& a, int kb, int grid, size_t smem, hipStream_t st) {
+static int launch_fwd(const XFwd& a, int kb, int grid, hipStream_t st) {
   switch (kb) {
 #define DS2_CASE(K)                                                                           \
   case K:                                                                                     \
-    hipLaunchKernelGGL((rnnx_fwd_kernel<CELL, MT, K>), dim3(grid), dim3(NTH), smem, st, a); \
+    hipLaunchKernelGGL((rnnx_fwd_kernel<CELL, MT, K>), dim3(grid), dim3(NTH), 0, st, a);      \
     break;
     DS2_CASE(1) DS2_CASE(2) DS2_CASE(3) DS2_CASE(4) DS2_CASE(5) DS2_CASE(6)
 #undef DS2_CASE
@@ -2453,37 +2453,41 @@ static int launch_fwd(const XFwd& a, int kb, int grid, size_t smem, hipStream_t 
   return (int)hipGetLastError();
 }
 
-template <typename F>
-static int set_smem_attr(F kernel, size_t smem) {
-  return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+// kernel arguments of a forward / BPTT launch from the descriptor; P: workgroups per group
+static XFwd make_xfwd(const DS2RnnX* d, int P) {
+  XFwd a;
+  a.T = d->T; a.N = d->N; a.NP = d->NP; a.H = d->H; a.P = P; a.BG = d->BG; a.R = d->R;
+  a.steps = d->steps; a.gstride = d->gstride; a.ngroups = d->ndir * d->BG;
+  a.xcd_map = d->xcd_map && a.ngroups <= 8; a.knobs = d->knobs;
+  a.lens = d->lens; a.gx = (const bf16_t*)d->gx;
+  for (int i = 0; i < 2; ++i) {
+    a.U[i] = (const bf16_t*)d->U[i]; a.bh[i] = d->bh[i]; a.y[i] = (bf16_t*)d->y[i];
+    a.hx[i] = (bf16_t*)d->ex[i]; a.hsave[i] = d->hsave[i]; a.gates[i] = d->gates[i];
+  }
+  a.ysum = (bf16_t*)d->ysum;
+  a.census = d->census; a.err = d->err; a.timeout = d->timeout; a.stamps = d->stamps;
+  return a;
+}
+
+static XBwdRS make_xbwd(const DS2RnnX* d, int P) {
+  XBwdRS a;
+  a.T = d->T; a.N = d->N; a.NP = d->NP; a.H = d->H; a.P = P; a.BG = d->BG; a.R = d->R;
+  a.steps = d->steps; a.gstride = d->gstride; a.ngroups = d->ndir * d->BG;
+  a.xcd_map = d->xcd_map && a.ngroups <= 8; a.knobs = d->knobs;
+  a.lens = d->lens; a.dy = (const bf16_t*)d->gx;
+  for (int i = 0; i < 2; ++i) {
+    a.U[i] = (const bf16_t*)d->U[i]; a.hsave[i] = d->hsave[i]; a.gates[i] = d->gates[i];
+    a.dgh[i] = (bf16_t*)d->ex[i]; a.ring[i] = (float*)d->ring[i];
+    a.dbx_part[i] = d->dbx_part[i]; a.dbh_part[i] = d->dbh_part[i];
+  }
+  a.dgx = (bf16_t*)d->dgx; a.dgx_scale = d->dgx_scale;
+  a.census = d->census; a.err = d->err; a.timeout = d->timeout; a.stamps = d->stamps;
+  return a;
 }
 
 }  // namespace
 
 extern "C" {
-
-struct DS2RnnX {
-  int T, N, NP, H, BG, R, steps, gstride, ndir, cell, mt, xcd_map, knobs;
-  const int* lens;
-  const void* gx;        // fwd: gx;  bwd: dy
-  const void* U[2];
-  const float* bh[2];
-  void* y[2];            // fwd: y
-  void* ex[2];           // fwd: hx exchange;  bwd: dgh exchange
-  float* hsave[2];
-  float* gates[2];
-  void* dgx;
-  float* dbx_part[2];
-  float* dbh_part[2];
-  float dgx_scale;
-  unsigned* census;
-  unsigned* err;
-  long long timeout;
-  unsigned long long* stamps;
-  void* ring[2];         // bwd reduce-scatter exchange ring (fp32, sentinel-filled)
-  void* ysum;            // fwd gen 4: fused direction sum (sentinel-filled) or null
-};
 
 // 1 if the forward launch for these parameters is generation 4 (which can fuse the
 // direction sum into its output stores)
@@ -2493,6 +2497,12 @@ struct DS2RnnX {
 static bool wide_ok(int H, int cell) { return cell == CELL_RELU && H % 32 == 0 && H / 32 > 32 && H <= 1792; }
 static int xcd_p(int H, int cell) { return wide_ok(H, cell) ? (H + UWW - 1) / UWW : H / UPW; }
 
+// k-steps register tile of the generation-2 forward (whole K per wave), -1 past 6
+static int gen2_kb(int H) {
+  const int need = (H / 32 + MW - 1) / MW;
+  return need <= 6 ? need : -1;
+}
+
 static bool gen4_ok(int H, int cell, int mt, int knobs) {
   const int kbq = (H / 32 + 3) / 4;
   if ((knobs & 256) || mt != 1) return false;
@@ -2500,14 +2510,12 @@ static bool gen4_ok(int H, int cell, int mt, int knobs) {
   return kbq <= 8;
 }
 
-int ds2_rnnx_kb(int H, int G, int fwd);
-
 // Which forward kernel family ds2_rnnx_fwd launches for a geometry (the dispatch below and
 // the report binding rnnx_fwd_family share this one function): 6 rnnw (wide one-gate), 5 rnne
 // (GRU, K-eighths), 4 rnnq (K-quarters), 2 rnnx (generation 2); 0 = not covered (-30/-31/-33)
 int ds2_rnnx_fwd_family(int H, int cell, int mt, int knobs) {
   if (wide_ok(H, cell)) return 6;
-  if (H % UPW != 0 || mt != 1 || ds2_rnnx_kb(H, cell == CELL_GRU ? 3 : 1, 1) < 0) return 0;
+  if (H % UPW != 0 || mt != 1 || gen2_kb(H) < 0) return 0;
   if (gen4_ok(H, cell, mt, knobs)) return (cell == CELL_GRU && H / 32 <= 32) ? 5 : 4;
   return 2;
 }
@@ -2529,33 +2537,9 @@ int ds2_rnnx_grid(int H, int cell, int ngroups, int xcd_map) {
   return (xcd_map && ngroups <= 8) ? 8 * P : ngroups * P;
 }
 
-// k-steps register tile of the generation-2 forward: whole K per wave
-int ds2_rnnx_kb(int H, int G, int fwd) {
-  (void)G;
-  if (!fwd) return -1;                                    // the gather BPTT was removed
-  const int need = (H / 32 + MW - 1) / MW;
-  return need <= 6 ? need : -1;
-}
-
-// dynamic LDS: none (the exchanged state goes straight into MFMA registers)
-size_t ds2_rnnx_smem(int H, int G, int mt, int fwd) {
-  (void)H; (void)G; (void)mt; (void)fwd;
-  return 0;
-}
-
 static int rnnw_fwd(const DS2RnnX* d, hipStream_t st) {
   if (d->R < 1 || d->R > 8 || d->mt != 1 || d->NP != d->BG * d->R) return -30;
-  XFwd a;
-  a.T = d->T; a.N = d->N; a.NP = d->NP; a.H = d->H; a.P = xcd_p(d->H, d->cell); a.BG = d->BG; a.R = d->R;
-  a.steps = d->steps; a.gstride = d->gstride; a.ngroups = d->ndir * d->BG;
-  a.xcd_map = d->xcd_map && a.ngroups <= 8; a.knobs = d->knobs;
-  a.lens = d->lens; a.gx = (const bf16_t*)d->gx;
-  for (int i = 0; i < 2; ++i) {
-    a.U[i] = (const bf16_t*)d->U[i]; a.bh[i] = d->bh[i]; a.y[i] = (bf16_t*)d->y[i];
-    a.hx[i] = (bf16_t*)d->ex[i]; a.hsave[i] = d->hsave[i]; a.gates[i] = d->gates[i];
-  }
-  a.ysum = (bf16_t*)d->ysum;
-  a.census = d->census; a.err = d->err; a.timeout = d->timeout; a.stamps = d->stamps;
+  const XFwd a = make_xfwd(d, xcd_p(d->H, d->cell));
   if (d->ysum != nullptr && d->ndir != 2) return -37;
   if (d->steps <= 0) return 0;
   const int grid = ds2_rnnx_grid(d->H, d->cell, a.ngroups, a.xcd_map);
@@ -2576,20 +2560,9 @@ static int rnnw_fwd(const DS2RnnX* d, hipStream_t st) {
 int ds2_rnnx_fwd(const DS2RnnX* d, hipStream_t st) {
   if (wide_ok(d->H, d->cell)) return rnnw_fwd(d, st);
   if (d->H % UPW != 0 || d->R < 1 || d->R > 16 * d->mt || d->NP != d->BG * d->R) return -30;
-  const int G = d->cell == CELL_GRU ? 3 : 1;
-  const int kb = ds2_rnnx_kb(d->H, G, 1);
+  const int kb = gen2_kb(d->H);
   if (kb < 0) return -31;
-  XFwd a;
-  a.T = d->T; a.N = d->N; a.NP = d->NP; a.H = d->H; a.P = d->H / UPW; a.BG = d->BG; a.R = d->R;
-  a.steps = d->steps; a.gstride = d->gstride; a.ngroups = d->ndir * d->BG;
-  a.xcd_map = d->xcd_map && a.ngroups <= 8; a.knobs = d->knobs;
-  a.lens = d->lens; a.gx = (const bf16_t*)d->gx;
-  for (int i = 0; i < 2; ++i) {
-    a.U[i] = (const bf16_t*)d->U[i]; a.bh[i] = d->bh[i]; a.y[i] = (bf16_t*)d->y[i];
-    a.hx[i] = (bf16_t*)d->ex[i]; a.hsave[i] = d->hsave[i]; a.gates[i] = d->gates[i];
-  }
-  a.ysum = (bf16_t*)d->ysum;
-  a.census = d->census; a.err = d->err; a.timeout = d->timeout; a.stamps = d->stamps;
+  const XFwd a = make_xfwd(d, d->H / UPW);
   if (d->steps <= 0) return 0;
   const int grid = ds2_rnnx_grid(d->H, d->cell, a.ngroups, a.xcd_map);
   // generation 4 (K-quarter split, register epilogue) unless knob 256 asks for generation 2
@@ -2640,24 +2613,9 @@ int ds2_rnnx_fwd(const DS2RnnX* d, hipStream_t st) {
 #undef DS2_Q
     return (int)hipGetLastError();
   }
-  const size_t smem = ds2_rnnx_smem(d->H, G, d->mt, 1);
-  int rc;
-#define DS2_FWD(C, M)                                                                        \
-  {                                                                                          \
-    switch (kb) {                                                                            \
-      case 1: rc = set_smem_attr(rnnx_fwd_kernel<C, M, 1>, smem); break;                     \
-      case 2: rc = set_smem_attr(rnnx_fwd_kernel<C, M, 2>, smem); break;                     \
-      case 3: rc = set_smem_attr(rnnx_fwd_kernel<C, M, 3>, smem); break;                     \
-      case 4: rc = set_smem_attr(rnnx_fwd_kernel<C, M, 4>, smem); break;                     \
-      case 5: rc = set_smem_attr(rnnx_fwd_kernel<C, M, 5>, smem); break;                     \
-      default: rc = set_smem_attr(rnnx_fwd_kernel<C, M, 6>, smem); break;                    \
-    }                                                                                        \
-    if (rc) return rc;                                                                       \
-    return launch_fwd<C, M>(a, kb, grid, smem, st);                                          \
-  }
+  // generation 2: no dynamic LDS (the exchanged state goes straight into MFMA registers)
   if (d->mt != 1) return -33;     // 16-row tiles only: the 32-row LDS footprint exceeds 160 KB
-  if (d->cell == CELL_GRU) DS2_FWD(CELL_GRU, 1) else DS2_FWD(CELL_RELU, 1)
-#undef DS2_FWD
+  return d->cell == CELL_GRU ? launch_fwd<CELL_GRU, 1>(a, kb, grid, st) : launch_fwd<CELL_RELU, 1>(a, kb, grid, st);
 }
 
 // floats of the reduce-scatter ring of ONE direction: [3 slots][BG][P][R][H]
@@ -2668,18 +2626,7 @@ static int rnnw_bwd(const DS2RnnX* d, hipStream_t st) {
   if (d->ring[0] == nullptr || (d->ndir == 2 && d->ring[1] == nullptr)) return -34;
   const int P = xcd_p(d->H, d->cell);
   if (P > 4 * MW) return -35;                         // GPT = 4 producers per gather thread
-  XBwdRS a;
-  a.T = d->T; a.N = d->N; a.NP = d->NP; a.H = d->H; a.P = P; a.BG = d->BG; a.R = d->R;
-  a.steps = d->steps; a.gstride = d->gstride; a.ngroups = d->ndir * d->BG;
-  a.xcd_map = d->xcd_map && a.ngroups <= 8; a.knobs = d->knobs;
-  a.lens = d->lens; a.dy = (const bf16_t*)d->gx;
-  for (int i = 0; i < 2; ++i) {
-    a.U[i] = (const bf16_t*)d->U[i]; a.hsave[i] = d->hsave[i]; a.gates[i] = d->gates[i];
-    a.dgh[i] = (bf16_t*)d->ex[i]; a.ring[i] = (float*)d->ring[i];
-    a.dbx_part[i] = d->dbx_part[i]; a.dbh_part[i] = d->dbh_part[i];
-  }
-  a.dgx = (bf16_t*)d->dgx; a.dgx_scale = d->dgx_scale;
-  a.census = d->census; a.err = d->err; a.timeout = d->timeout; a.stamps = d->stamps;
+  const XBwdRS a = make_xbwd(d, P);
   if (d->steps <= 0) return 0;
   const int grid = ds2_rnnx_grid(d->H, d->cell, a.ngroups, a.xcd_map);
   const int npw = (d->H / 32 + MW - 1) / MW;          // unit pairs per publishing wave
@@ -2704,18 +2651,7 @@ int ds2_rnnx_bwd_rs(const DS2RnnX* d, hipStream_t st) {
   const int P = d->H / UPW;
   if (P > 6 * MW) return -35;                       // at most GPT = 6 producers per gather thread
   const int mtu_need = (d->H / 16 + MW - 1) / MW;
-  XBwdRS a;
-  a.T = d->T; a.N = d->N; a.NP = d->NP; a.H = d->H; a.P = P; a.BG = d->BG; a.R = d->R;
-  a.steps = d->steps; a.gstride = d->gstride; a.ngroups = d->ndir * d->BG;
-  a.xcd_map = d->xcd_map && a.ngroups <= 8; a.knobs = d->knobs;
-  a.lens = d->lens; a.dy = (const bf16_t*)d->gx;
-  for (int i = 0; i < 2; ++i) {
-    a.U[i] = (const bf16_t*)d->U[i]; a.hsave[i] = d->hsave[i]; a.gates[i] = d->gates[i];
-    a.dgh[i] = (bf16_t*)d->ex[i]; a.ring[i] = (float*)d->ring[i];
-    a.dbx_part[i] = d->dbx_part[i]; a.dbh_part[i] = d->dbh_part[i];
-  }
-  a.dgx = (bf16_t*)d->dgx; a.dgx_scale = d->dgx_scale;
-  a.census = d->census; a.err = d->err; a.timeout = d->timeout; a.stamps = d->stamps;
+  const XBwdRS a = make_xbwd(d, P);
   if (d->steps <= 0) return 0;
   const int grid = ds2_rnnx_grid(d->H, d->cell, a.ngroups, a.xcd_map);
   // bf16 partials (knob 64: fp32): PBF 1 for R <= 8 (two producers per load), 2 for R <= 16

@@ -42,12 +42,11 @@ _conv_streams = {}
 
 
 def _conv_side_stream(dev, w):
-    """The conv2 weight-gradient stream, or None (off, no GPU, a single-stream capture, or a
-    gradient bucketer attached: the data-parallel step measured 9.36-9.44 ms/step with it
-    against 7.63 without at world 1, scripts/r6_dpcheck.sh, so DP keeps it in line)."""
+    """The conv2 weight-gradient stream, or None (off, no GPU, or a gradient bucketer attached:
+    the data-parallel step measured 9.36-9.44 ms/step with it against 7.63 without at world 1,
+    scripts/r6_dpcheck.sh, so DP keeps it in line)."""
     a = arena_of(w)
-    if not _CONV_WSIDE or dev.type != "cuda" or (a is not None and (a.wgrad.single_stream or
-                                                                  getattr(a, "_ready_cbs", None))):
+    if not _CONV_WSIDE or dev.type != "cuda" or (a is not None and getattr(a, "_ready_cbs", None)):
         return None
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
     s = _conv_streams.get(idx)

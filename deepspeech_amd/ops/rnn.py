@@ -140,15 +140,11 @@ _DU_SPLITS = 2
 LDS_BYTES = 160 * 1024
 
 
-def _xcd_kb(H: int, G: int, fwd: bool) -> int:
-    """k-steps per MFMA wave of csrc/rnn_xcd.hip (K split over the 7 worker waves; the
-    8th is the memory wave). -1 if the tile would not fit."""
-    need = -(-((H if fwd else G * H) // 32) // 7)
-    opts = (1, 2, 3, 4, 5, 6) if fwd else (2, 4, 6, 8, 11)
-    for k in opts:
-        if k >= need:
-            return k
-    return -1
+def _xcd_kb(H: int) -> int:
+    """k-steps per MFMA wave of the generation-2 forward of csrc/rnn_xcd.hip (K split over the
+    7 worker waves; the 8th is the memory wave). -1 if the tile would not fit."""
+    need = -(-(H // 32) // 7)
+    return need if need <= 6 else -1
 
 
 def _rs_ok(H: int) -> bool:
@@ -163,7 +159,7 @@ def _rs_ok(H: int) -> bool:
 
 def _xcd_lds(H: int, G: int, mt: int) -> int:
     """Static LDS bytes of the larger of the two csrc/rnn_xcd.hip kernels (16-row tiles only)."""
-    if mt != 1 or _xcd_kb(H, G, True) < 0 or not _rs_ok(H):
+    if mt != 1 or _xcd_kb(H) < 0 or not _rs_ok(H):
         return 1 << 30
     # forward + reduce-scatter BPTT (static, ~61 KB at G = 3)
     return 2 * 7 * 16 * (G * 32 + 1) * 4 + 16 * 32 * 2 + 2 * 16 * G * 32 * 4 + 2 * 2 * 16 * 32 * 4 \
@@ -530,7 +526,7 @@ def _run_fwd(gx, lens, U, bh, plan: RnnPlan, h0=None, bufs: Optional[_FwdBufs] =
                    gates[1] if (gates is not None and d1) else None,
                    census, err, T, N, plan.NP, H, plan.BG, plan.R, steps, gstride, ndir,
                    CELL_CODE[plan.cell], plan.mt, TIMEOUT_TICKS, plan.xcd_map, _kernel_knobs(plan),
-                   _stamps("fwd", plan, int(C.rnnx_info(H, GATES[plan.cell], plan.mt, ndir * plan.BG,
+                   _stamps("fwd", plan, int(C.rnnx_info(H, GATES[plan.cell], ndir * plan.BG,
                                                          plan.xcd_map)["grid"]), dev), ysum)
         y = ysum if fuse else (torch.add(y2[0], y2[1]) if d1 else y2[0])
         return y, (hx, hs, gates if gates is not None else torch.empty(0, device=dev))
@@ -746,7 +742,7 @@ def _run_bwd(dy, lens, U, hx, hs, gates, plan: RnnPlan, gstride: int, dgx_scale:
                    parts[1] if (parts is not None and plan.cell == "gru") else None,
                    float(dgx_scale), census, err, T, N, plan.NP, H, plan.BG, plan.R, steps, gstride, ndir,
                    CELL_CODE[plan.cell], plan.mt, TIMEOUT_TICKS, plan.xcd_map, _kernel_knobs(plan),
-                   _stamps("bwd", plan, int(C.rnnx_info(H, G, plan.mt, ndir * plan.BG, plan.xcd_map)["grid"]), dev),
+                   _stamps("bwd", plan, int(C.rnnx_info(H, G, ndir * plan.BG, plan.xcd_map)["grid"]), dev),
                    ring[0], ring[1] if d1 else None)
         return dgx, dgh, parts
     err = error_word(dev)
@@ -1366,8 +1362,8 @@ class WgradScheduler:
     queue of pending GEMMs (this state used to be module-global).
 
     * ``stream(device)``: side stream for the recurrent layers' (and head's / front-end's)
-      weight-gradient GEMMs (``single_stream`` keeps them on the current stream). The
-      Trainer joins it (:meth:`join`) before the optimizer reads the gradients.
+      weight-gradient GEMMs. The Trainer joins it (:meth:`join`) before the optimizer reads
+      the gradients.
     * Single device (``set_deferral``): every recurrent layer's weight gradients (dW = dgx^T x
       and both directions' dU = dgh^T h) are deferred until the bottom layer's BPTT has been
       issued, and then run as one grouped gemm8 launch on the side stream, beside the conv
@@ -1378,10 +1374,6 @@ class WgradScheduler:
       overrides); the GEMMs then run per layer on the side stream as each BPTT finishes.
     * ``set_early_update``: the optimizer range of the parameters that are final once the
       grouped launch is issued runs on the side stream right behind it.
-    * ``set_fused_update``: the grouped launch applies Adam + EMA to its members' elements in
-      its epilogue (csrc/gemm8.hip) instead of storing their gradients; ``fused_ranges`` then
-      lists the arena element ranges already updated this step, which every later optimizer
-      range of the step skips.
     """
 
     def __init__(self):
@@ -1405,20 +1397,15 @@ class WgradScheduler:
         self._t_events = {}        # device -> event of the last transposes flush
         self._t_waited = set()     # streams that waited for it
         self._hold = []            # tensors read on the side stream, released by join()
-        self._fused = None         # (arena, tensors, constants, store_g): set_fused_update
-        self.fused_ranges = []     # arena element ranges the grouped epilogue updated this step
         # Trainer defer_update (carry_du): the recurrent layers above the upper trigger hand their
         # beside dU GEMM to the next step's forward (carried_du: layer -> fn(grid), taken by the
         # Trainer with take_carried_du; whatever is not taken runs before this step's optimizer)
         self.carry_du = False
         self.carried_du = {}
-        # every weight gradient on the current stream (a captured step graph: ROCm replays a
-        # graph's cross-stream edges as barrier packets between its queues)
-        self.single_stream = False
         _schedulers.add(self)
 
     def stream(self, device: torch.device) -> Optional["torch.cuda.Stream"]:
-        if device.type != "cuda" or self.single_stream:
+        if device.type != "cuda":
             return None
         idx = device.index if device.index is not None else torch.cuda.current_device()
         s = self.streams.get(idx)
@@ -1441,9 +1428,8 @@ class WgradScheduler:
     def discard(self) -> None:
         """Drop deferred GEMMs of an aborted backward (called at the start of a step)."""
         if self._hold:
-            if not self.single_stream:
-                for idx, s in self.streams.items():
-                    _stream_wait(torch.cuda.current_stream(idx), s)
+            for idx, s in self.streams.items():
+                _stream_wait(torch.cuda.current_stream(idx), s)
             self._hold.clear()
         self.deferred.clear()
         self.main_tail.clear()
@@ -1454,8 +1440,6 @@ class WgradScheduler:
         self.early_upper_done = False
         self.early_upper_hi = 0
         self.transposes.clear()
-        self._fused = None
-        self.fused_ranges = []
         self.carried_du = {}
 
     def flush_transposes(self) -> None:
@@ -1559,46 +1543,18 @@ class WgradScheduler:
             self.carried_du[k](0)
         self.carried_du = {}
 
-    def set_fused_update(self, arena, tensors, constants, store_g: bool = False) -> None:
-        """For THIS backward: the grouped tail launch applies the optimizer to its members'
-        elements in its epilogue (tensors / constants as gemm.gemm8_group's ``opt``)."""
-        self._fused = (arena, list(tensors), list(constants), bool(store_g))
-        self.fused_ranges = []
-
-    def _fused_opt(self, members):
-        """gemm8_group ``opt`` for these members, or None when the epilogue cannot take them
-        (not all contiguous, 16-B aligned first-write views of this arena's gradient buffer)."""
-        if self._fused is None:
-            return None
-        arena, tensors, constants, store_g = self._fused
-        g = arena.grad
-        base, n = g.data_ptr(), g.numel()
-        ranges = []
-        for _, _, out in members:
-            e0 = (out.data_ptr() - base) // 4
-            if (out.dtype != torch.float32 or not out.is_contiguous() or (out.data_ptr() - base) % 16 or
-                    e0 < 0 or e0 + out.numel() > n or out.shape[-1] % 4):
-                return None
-            ranges.append((e0, e0 + out.numel()))
-        return (tensors, constants, store_g), ranges
-
     def flush(self) -> None:
         """Issue every deferred weight-gradient GEMM on the current stream: one grouped launch
         when every one of them can join it, else one call each."""
         if self.deferred and self.grouped and all(isinstance(d, Deferred) and d.members for d in self.deferred):
             items, self.deferred = self.deferred, []
             members = [m for d in items for m in d.members]
-            fused = self._fused_opt(members)
             # the grouped launch on 3/4 of the CUs: the conv front-end's backward beside it
             # (LDS-bound kernels that cannot share a CU with a group workgroup's 128 KB) gets
             # the rest; headline, same box: 7.83-7.87 ms/step vs 7.89-7.90 on every CU, 7.94
             # at 176, 7.84-7.92 at 208, 8.03 at 128
             cap = _GROUP_CAP or (3 * _ext.num_cus(torch.cuda.current_device())) // 4   # schedule group_cap
-            if fused is not None:
-                GM.gemm8_group(members, opt=fused[0], max_grid=cap)
-                self.fused_ranges.extend(fused[1])
-            else:
-                GM.gemm8_group(members, max_grid=cap)
+            GM.gemm8_group(members, max_grid=cap)
             for d in items:
                 d.done()
             return
@@ -1655,9 +1611,8 @@ class WgradScheduler:
     def join(self) -> None:
         """Make the current stream wait for every pending side-stream weight gradient."""
         self.drain()
-        if not self.single_stream:
-            for idx, s in self.streams.items():
-                _stream_wait(torch.cuda.current_stream(idx), s)
+        for idx, s in self.streams.items():
+            _stream_wait(torch.cuda.current_stream(idx), s)
         self._hold.clear()           # frees on the current stream, ordered after the side work
 
 

@@ -55,32 +55,20 @@ def lr_schedule_from_args(args, steps_per_epoch: int) -> LRSchedule:
                       args.lr_decay_factor)
 
 
-# Optimizer range of the head + layers >= 1 beside layer 0's BPTT when the weight gradients are
-# not deferred, on a capped grid (same box, config 5 fp8, 2 rounds: off 21.77 / 21.39 ms/step,
-# full grid 21.16 / 21.08, 192 blocks 21.04 / 20.99, 512 blocks 21.04 / 20.98)
-_EARLY_UPPER = True
+# Grid cap (blocks) of the optimizer range of the head + layers >= 1, which runs beside layer 0's
+# BPTT when the weight gradients are not deferred (same box, config 5 fp8, 2 rounds: without that
+# early range 21.77 / 21.39 ms/step, full grid 21.16 / 21.08, 192 blocks 21.04 / 20.99, 512 blocks
+# 21.04 / 20.98)
 _UPPER_GRID = 512
-# single device, weight gradients deferred to the grouped tail launch: that launch can apply Adam +
-# EMA to the recurrent weights in its epilogue (csrc/gemm8.hip "Fused optimizer epilogue")
-# instead of storing their gradients for a separate optimizer pass to read back. Bitwise the
-# same update (tests/test_gemm_gpu.py), but measured slower at the headline (same box, round 4:
-# 8.21 vs 8.04 ms/step): the grid's workgroups finish their tiles in lockstep, so every
-# epilogue streams its 2.2 MB of optimizer state at the same moment (HBM-bound, +450 us on the
-# group) instead of overlapping the MFMA work; off until that is staggered
-_FUSED_OPT = False
-# grid cap (blocks) of that early optimizer range: it streams beside the conv front-end's
-# backward, whose latency-bound conv1 weight gradient it slowed 3x on the full grid (headline,
-# same box, 4 rounds: 7.745-7.773 ms/step at 384 vs 7.788-7.817 uncapped and 7.793-7.821 at 512;
-# another box 3 rounds: 384 -0.45 %, 256 -0.2 to -0.3 %). Only when the range is the whole head
-# + recurrent stack (every weight gradient deferred to the grouped tail): config 5, whose upper
-# range already ran beside layer 0's BPTT, measured +0.15-0.3 % with the cap on its remainder.
+# grid cap (blocks) of the early optimizer range of the head + recurrent stack on a single device
+# (Trainer._body): it streams beside the conv front-end's backward, whose latency-bound conv1
+# weight gradient it slowed 3x on the full grid (headline, same box, 4 rounds: 7.745-7.773
+# ms/step at 384 vs 7.788-7.817 uncapped and 7.793-7.821 at 512; another box 3 rounds: 384
+# -0.45 %, 256 -0.2 to -0.3 %). Only when the range is the whole head + recurrent stack (every
+# weight gradient deferred to the grouped tail): config 5, whose upper range already ran beside
+# layer 0's BPTT, measured +0.15-0.3 % with the cap on its remainder, so that remainder runs
+# uncapped.
 _EARLY_GRID = 384
-# the same range when the upper part already ran beside layer 0's BPTT (0: uncapped)
-_LOWER_GRID = 0
-# grid cap (blocks) of the data-parallel per-bucket Adam + EMA ranges, which stream beside the
-# BPTTs (0: uncapped). --force_dp at world 1, same box, 3 rounds: uncapped 7.754 / 7.747 / 7.705,
-# 512 7.782 / 7.725 / 7.719, 256 7.771 / 7.790 / 7.814, 128 7.86-7.88 ms/step
-_BUCKET_GRID = 0
 # with defer_update, the beside dU GEMMs of the layers above the upper trigger go to the next
 # step's forward too (ops/rnn.py WgradScheduler.carry_du)
 _CARRY_DU = True
@@ -90,9 +78,6 @@ _CARRY_DU = True
 # 4 blocks + 32 KB 7.432-7.435
 _CARRY_BLOCKS_PER_CU = 1
 _CARRY_LDS = 0
-# capture step graphs on one stream (False: the weight-gradient side stream too; single-stream
-# capture is not bitwise at H = 800, where the deferral needs the side stream)
-_GRAPH_SINGLE_STREAM = False
 
 
 def _check_hw_queues() -> None:
@@ -185,9 +170,6 @@ class Trainer:
         # data parallel: optimizer ranges per gradient bucket behind its all-reduce
         # (GradBucketer.set_optimizer); per_bucket_update=False keeps one update after finish()
         self.per_bucket_update = True
-        # keep_grads: the fused optimizer epilogue also stores the gradients it consumed (set
-        # when something reads arena.grad after a step: gradient summaries)
-        self.keep_grads = False
         # single device: arena elements [0, split) — FC head and recurrent stack, laid out
         # before the conv front-end in gradient-production order — get their optimizer update
         # as soon as the recurrent weight gradients are issued (Trainer.step)
@@ -327,7 +309,7 @@ class Trainer:
         warm-up steps before any capture. gloo cannot be captured: its process groups keep the
         eager step."""
         if not (bool(self.step_graphs) and self.arena.flat.is_cuda and self.model.engine == "hip"
-                and not _FUSED_OPT and not getattr(self.model, "capture", False)):   # taps: eager
+                and not getattr(self.model, "capture", False)):   # taps: eager
             return False
         if not self.bucketer.enabled:
             return self.world == 1
@@ -476,15 +458,14 @@ class Trainer:
         graph = torch.cuda.CUDAGraph()
         torch.cuda.synchronize(dev)
         self.opt.device_hyper = True
-        sch = self.arena.wgrad
-        sch.single_stream = _GRAPH_SINGLE_STREAM
         try:
-            # thread_local: the train driver's prefetch thread may pin / copy while we capture
+            # thread_local: the train driver's prefetch thread may pin / copy while we capture.
+            # The weight-gradient side stream is captured too: single-stream capture is not
+            # bitwise at H = 800, where the deferral needs the side stream
             with torch.cuda.graph(graph, pool=self._graph_pool, capture_error_mode="thread_local"):
                 loss = self._body(static, 0.0, 0.0)
         finally:
             self.opt.device_hyper = False
-            sch.single_stream = False
         return _StepGraph(graph, static["feats"], static["seq_lens"], static["labels"], static["label_lens"], loss,
                           self._state_ptrs())
 
@@ -539,10 +520,11 @@ class Trainer:
             # DP-native ordering: each gradient bucket's Adam + EMA range runs on the
             # bucketer's ordering stream right behind its all-reduce (bitwise the same update);
             # with defer_update, the head's and upper layers' buckets carry theirs into the next
-            # forward (GradBucketer carry_hi)
+            # forward (GradBucketer carry_hi). The ranges stream beside the BPTTs on an uncapped
+            # grid (--force_dp at world 1, same box, 3 rounds: uncapped 7.754 / 7.747 / 7.705,
+            # 512 blocks 7.782 / 7.725 / 7.719, 256 7.771 / 7.790 / 7.814, 128 7.86-7.88 ms/step)
             up = self.upper_range(1) if dp_carry else None
-            self.bucketer.set_optimizer(lambda lo, hi: self.opt.apply_range(lo, hi, lr_t, keep, gscale,
-                                                                            max_grid=_BUCKET_GRID),
+            self.bucketer.set_optimizer(lambda lo, hi: self.opt.apply_range(lo, hi, lr_t, keep, gscale),
                                         carry_hi=up[0] if up else 0)
         early = (not per_bucket and self.nan_policy != "skip" and self._early_split > 0 and lazy and
                  self.arena.wgrad.grouped and self.arena.wgrad.defer_input)
@@ -555,15 +537,13 @@ class Trainer:
             # weight-gradient stream right after the grouped tail GEMMs, beside the conv
             # front-end's backward (WgradScheduler.set_early_update); the front-end's range after
             split, sch = self._early_split, self.arena.wgrad
-            if _FUSED_OPT:
-                tensors, consts = self.opt.fused_constants(lr_t, keep, gscale)
-                sch.set_fused_update(self.arena, tensors, consts, store_g=self.keep_grads)
+            # (capped grid only for the whole range: see _EARLY_GRID)
             self.arena.wgrad.set_early_update(
-                lambda: self.opt.apply_excluding(sch.early_upper_hi if sch.early_upper_done else 0, split,
-                                                 sch.fused_ranges, lr_t, keep, gscale,
-                                                 max_grid=_LOWER_GRID if sch.early_upper_done else _EARLY_GRID),
+                lambda: self.opt.apply_range(sch.early_upper_hi if sch.early_upper_done else 0, split,
+                                             lr_t, keep, gscale,
+                                             max_grid=0 if sch.early_upper_done else _EARLY_GRID),
                 self._early_params)
-            if self._layer_first and _EARLY_UPPER:
+            if self._layer_first:
                 # the head and the layers whose weight gradients ran beside the BPTT (not in the
                 # grouped tail launch): their range goes out beside the next BPTT, on a capped grid,
                 # or (defer_update) beside the next step's first recurrence
@@ -592,7 +572,7 @@ class Trainer:
                 # when the lower early range was skipped: never apply it twice
                 sch = self.arena.wgrad
                 lo = split if sch.early_done else (sch.early_upper_hi if sch.early_upper_done else 0)
-                self.opt.apply_excluding(lo, self.arena.numel, sch.fused_ranges, lr_t, keep, gscale)
+                self.opt.apply_range(lo, self.arena.numel, lr_t, keep, gscale)
             if carried[0] > 0:
                 self._carry_update(carried[0], lr_t, keep, gscale, carried_du)
         elif not per_bucket:

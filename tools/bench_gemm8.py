@@ -176,7 +176,7 @@ def main():
         cases[name + " | gemm8 each"] = (fl, each)
         cases[name + " | gemm8 group"] = (fl, lambda mem=mem: G.gemm8_group(mem))
         # the same group writing views of ONE gradient arena, then the optimizer over those
-        # elements (separate streaming Adam + EMA launch) vs the fused optimizer epilogue
+        # elements (separate streaming Adam + EMA launch)
         n = sum(o.numel() for _, _, o in mem)
         ar = dict(g=torch.zeros(n, device=dev), p=torch.randn(n, device=dev), m=torch.zeros(n, device=dev),
                   v=torch.zeros(n, device=dev), e=torch.randn(n, device=dev),
@@ -191,9 +191,7 @@ def main():
             G.gemm8_group(amem)
             Cx.adam_ema(ar["p"], ar["g"], ar["m"], ar["v"], ar["e"], ar["p16"], 1e-4, 0.9, 0.999, 1e-8, 1.0, 0.999,
                         None, 0)
-        opt = ([ar["p"], ar["m"], ar["v"], ar["e"], ar["p16"], ar["g"]], [1e-4, 0.9, 0.999, 1e-8, 1.0, 0.999], False)
         cases[name + " | gemm8 group + adam"] = (fl, sep)
-        cases[name + " | gemm8 group fused adam"] = (fl, lambda amem=amem, opt=opt: G.gemm8_group(amem, opt=opt))
         cases[name + " | adam alone"] = (fl, lambda ar=ar: Cx.adam_ema(
             ar["p"], ar["g"], ar["m"], ar["v"], ar["e"], ar["p16"], 1e-4, 0.9, 0.999, 1e-8, 1.0, 0.999, None, 0))
     res = {k: [] for k in cases}
