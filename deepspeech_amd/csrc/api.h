@@ -195,6 +195,16 @@ int ds2_ctc_beam_backtrack(const void* nodes, int cap, const int* node, const in
                            const float* pnb, int B, int W, int* out, int* out_len, float* score, int Lcap,
                            hipStream_t st);
 
+// ---- align.hip --------------------------------------------------------------------------
+// CTC forced alignment (Viterbi path + backtrack). em [T, N, K] fp32 / bf16 (log_probs != 0: used
+// as they are, else log-softmaxed), labels [N, Lmax] (Lmax >= 1); outputs path [N, T],
+// tok_start / tok_end / tok_score [N, Lmax], score [N]; ws of ds2_ctc_align_ws_bytes bytes.
+// Returns -20 for K > 32, -21 for 2*Lmax+1 > 2048 (ws_bytes: -1), -22 for a blank outside [0, K).
+long long ds2_ctc_align_ws_bytes(int T, int N, int Lmax);
+int ds2_ctc_align(const void* em, int em_bf16, int log_probs, const int* lens, const int* labels,
+                  const int* label_lens, int* path, int* tok_start, int* tok_end, float* tok_score, float* score,
+                  void* ws, int T, int N, int K, int Lmax, int blank, hipStream_t st);
+
 // ---- bn_act.hip -------------------------------------------------------------------------
 int ds2_bn_stats(const void* y, int y_bf16, int N, int C, int T, int F, float* part, int nb, float eps, float* mean,
                  float* invstd, float* run_mean, float* run_var, float momentum, hipStream_t st);

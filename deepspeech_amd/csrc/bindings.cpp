@@ -466,6 +466,52 @@ void ctc_fused(at::Tensor logits, at::Tensor lens, at::Tensor labels, at::Tensor
         "ctc_fused");
 }
 
+// --------------------------------------------------------------------------- CTC forced alignment
+int64_t ctc_align_ws_bytes(int64_t T, int64_t N, int64_t Lmax) {
+  return ds2_ctc_align_ws_bytes((int)T, (int)N, (int)Lmax);
+}
+
+// emissions [T, N, K] (fp32 / bf16) -> path [N, T] int32, tok_start / tok_end [N, Lmax] int32,
+// tok_score [N, Lmax] fp32, score [N] fp32 (csrc/align.hip)
+void ctc_align(at::Tensor em, at::Tensor lens, at::Tensor labels, at::Tensor label_lens, at::Tensor path,
+               at::Tensor tok_start, at::Tensor tok_end, at::Tensor tok_score, at::Tensor score, at::Tensor ws,
+               int64_t blank, bool log_probs) {
+  need_gpu(em, "emissions");
+  need_gpu(labels, "labels");
+  need_gpu(ws, "ws");
+  TORCH_CHECK(em.dim() == 3, "emissions must be [T, N, K]");
+  const int T = (int)em.size(0), N = (int)em.size(1), K = (int)em.size(2);
+  TORCH_CHECK(labels.dim() == 2 && labels.scalar_type() == at::kInt, "labels must be int32 [N, Lmax]");
+  const int Lmax = (int)labels.size(1);
+  TORCH_CHECK(K <= 32, "ctc_align: K <= 32 classes");
+  TORCH_CHECK(Lmax >= 1 && 2 * (int64_t)Lmax + 1 <= 2048, "ctc_align: 1 <= Lmax and 2*Lmax+1 <= 2048 lattice states");
+  TORCH_CHECK(blank >= 0 && blank < K, "ctc_align: 0 <= blank < K");
+  TORCH_CHECK(labels.size(0) == N && lens.numel() == N && label_lens.numel() == N, "batch mismatch");
+  for (const at::Tensor* t : {&lens, &label_lens}) {
+    need_gpu(*t, "lens / label_lens");
+    TORCH_CHECK(t->scalar_type() == at::kInt, "lens / label_lens must be int32");
+  }
+  for (const at::Tensor* t : {&path, &tok_start, &tok_end}) {
+    need_gpu(*t, "path / tok_start / tok_end");
+    TORCH_CHECK(t->scalar_type() == at::kInt, "path / tok_start / tok_end must be int32");
+  }
+  need_gpu(tok_score, "tok_score");
+  need_gpu(score, "score");
+  TORCH_CHECK(tok_score.scalar_type() == at::kFloat && score.scalar_type() == at::kFloat, "scores must be fp32");
+  TORCH_CHECK(path.numel() == (int64_t)N * T, "path must be [N, T]");
+  TORCH_CHECK(tok_start.numel() == (int64_t)N * Lmax && tok_end.numel() == (int64_t)N * Lmax &&
+                  tok_score.numel() == (int64_t)N * Lmax, "tok_start / tok_end / tok_score must be [N, Lmax]");
+  TORCH_CHECK(score.numel() == N, "score must be [N]");
+  TORCH_CHECK(ws.scalar_type() == at::kByte && ws.numel() >= ds2_ctc_align_ws_bytes(T, N, Lmax) &&
+                  (reinterpret_cast<uintptr_t>(ws.data_ptr()) & 15) == 0,
+              "alignment workspace too small or not 16-B aligned");
+  check(ds2_ctc_align(em.data_ptr(), is_bf16(em), log_probs ? 1 : 0, lens.data_ptr<int>(), labels.data_ptr<int>(),
+                      label_lens.data_ptr<int>(), path.data_ptr<int>(), tok_start.data_ptr<int>(),
+                      tok_end.data_ptr<int>(), tok_score.data_ptr<float>(), score.data_ptr<float>(), ws.data_ptr(), T,
+                      N, K, Lmax, (int)blank, cur_stream()),
+        "ctc_align");
+}
+
 // --------------------------------------------------------------------------- BN
 int64_t bn_chunks(int64_t N, int64_t T, int64_t F) { return ds2_bn_chunks((int)N, (int)T, (int)F); }
 
@@ -1400,6 +1446,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("rnnx_ring_floats", [](int64_t H, int64_t BG, int64_t R) { return ds2_rnnx_ring_floats((int)H, (int)BG, (int)R); });
   m.def("ctc_fused", &ctc_fused);
   m.def("ctc_ws_floats", &ctc_ws_floats);
+  m.def("ctc_align", &ctc_align);
+  m.def("ctc_align_ws_bytes", &ctc_align_ws_bytes);
   m.def("bn_chunks", &bn_chunks);
   m.def("bn_stats", &bn_stats);
   m.def("bn_apply", &bn_apply);

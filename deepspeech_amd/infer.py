@@ -236,6 +236,26 @@ class StreamingRecognizer:
             return [list(g) for g in self.greedy]
         return self.beams.best()
 
+    @torch.no_grad()
+    def finish_timed(self):
+        """Words with times per stream: the final hypothesis of the configured decoder (as
+        finish() returns it) force-aligned against the stream's stored log-probs
+        (ops/align.py ctc_forced_align, on the device where they are; time convention in
+        align.py). The alignment itself is kept in ``self.alignment``."""
+        from .align import HOP_S, _pad_labels, tokens_to_words
+        from .ops.align import ctc_forced_align
+        hyp = self.finish()
+        self.alignment = None
+        if not self.logprobs:
+            return [[] for _ in range(self.B)]
+        lp = torch.cat(self.logprobs, 0)                        # [T2, B, K] log-probs
+        lens = torch.full((self.B,), lp.shape[0], dtype=torch.int32, device=lp.device)
+        labels, label_lens = _pad_labels(hyp)
+        al = ctc_forced_align(lp, lens, labels.to(lp.device), label_lens.to(lp.device), BLANK, log_probs=True)
+        self.alignment = al
+        duration = HOP_S * self.total
+        return [tokens_to_words(al, hyp, b, duration) for b in range(self.B)]
+
 
 def rtf(model: DeepSpeech2, seconds: float = 10.0, chunk_s: float = 1.0, batch: int = 1,
         decoder: str = "greedy", beam_width: int = 16, seed: int = 0, audio: bool = False):

@@ -196,3 +196,105 @@ def greedy_decode(logits: torch.Tensor, lens: torch.Tensor, blank: int = BLANK) 
             prev = c
         out.append(res)
     return out
+
+
+# ---------------------------------------------------------------------------------
+# CTC forced alignment (the oracle of csrc/align.hip)
+# ---------------------------------------------------------------------------------
+def ctc_viterbi_ref(log_probs: torch.Tensor, lens, labels, label_lens, blank: int = BLANK):
+    """Best CTC path of each utterance's labels through ``log_probs`` [T, N, K] (natural-log
+    probabilities, used as they are after widening to fp32).
+
+    Lattice states s = 0 .. 2L (even = blank, odd = label s >> 1), start in state 0 or 1, end in
+    state 2L or 2L-1:
+
+        v_t(s) = max(v_{t-1}(s), v_{t-1}(s-1), [v_{t-1}(s-2) if s odd and label != label of s-2])
+                 + lp_t(class(s))
+
+    in fp32, ``max`` first and then ONE add per state and frame: the operations of the kernel in
+    the kernel's order, so ``score`` is bitwise the kernel's on the same log-probs.
+    Tie rule: on equal values stay (s), then s-1, then s-2 (strict ``>`` in that order); at the
+    end state 2L wins over 2L-1 unless 2L-1 is strictly better.
+
+    Returns (path [N, T] int32, tok_start [N, Lmax] int32, tok_end [N, Lmax] int32,
+    tok_score [N, Lmax] fp32, score [N] fp32) as CPU tensors, Lmax = max(1, labels.shape[1]):
+    ``path`` is the class on the best path per frame (-1 for t >= len), ``tok_start`` /
+    ``tok_end`` the first / last frame (inclusive) spent in each label's state and
+    ``tok_score`` the sum of lp over those frames (-1 / -1 / 0 at and past ``label_lens``),
+    ``score`` the path's total log-probability. An utterance without a finite path (len <= 0,
+    fewer frames than labels + adjacent equal labels, -inf on every path) has score -inf,
+    path -1 and spans -1; a NaN in a valid frame gives score NaN (as it makes the CTC loss
+    NaN), path -1 and spans -1."""
+    import numpy as np
+    lp_all = log_probs.detach().to(torch.float32).cpu().numpy()
+    T, N, K = lp_all.shape
+    lens = np.asarray(torch.as_tensor(lens).cpu().numpy(), dtype=np.int64).reshape(N)
+    label_lens = np.asarray(torch.as_tensor(label_lens).cpu().numpy(), dtype=np.int64).reshape(N)
+    labels = np.asarray(torch.as_tensor(labels).cpu().numpy(), dtype=np.int64).reshape(N, -1)
+    Lw = labels.shape[1]
+    Lmax = max(1, Lw)
+    path = np.full((N, T), -1, np.int32)
+    tok_start = np.full((N, Lmax), -1, np.int32)
+    tok_end = np.full((N, Lmax), -1, np.int32)
+    tok_score = np.zeros((N, Lmax), np.float32)
+    score = np.full((N,), -np.inf, np.float32)
+    ninf = np.float32(-np.inf)
+    for b in range(N):
+        n = int(min(lens[b], T))
+        L = int(max(0, min(label_lens[b], Lw)))
+        if n <= 0 or L > n:
+            continue
+        lab = labels[b, :L]
+        if L and (lab.min() < 0 or lab.max() >= K):
+            continue                                  # no finite path through a class that is not there
+        S = 2 * L + 1
+        cls = np.full(S, blank, np.int64)
+        cls[1::2] = lab
+        skip = np.zeros(S, bool)
+        skip[3::2] = lab[1:] != lab[:-1]
+        lp = lp_all[:n, b]                            # [n, K] fp32
+        if np.isnan(lp).any():
+            score[b] = np.float32(np.nan)
+            continue
+        em = lp[:, cls]                               # [n, S]
+        v = np.full(S, ninf, np.float32)
+        v[:2] = em[0, :2]
+        bp = np.zeros((n, S), np.int8)
+        with np.errstate(invalid="ignore"):
+            for t in range(1, n):
+                a1 = np.full(S, ninf, np.float32)
+                a1[1:] = v[:-1]
+                a2 = np.full(S, ninf, np.float32)
+                a2[2:] = v[:-2]
+                a2 = np.where(skip, a2, ninf)
+                best, k = v, np.zeros(S, np.int8)
+                m = a1 > best
+                best, k = np.where(m, a1, best), np.where(m, np.int8(1), k)
+                m = a2 > best
+                best, k = np.where(m, a2, best), np.where(m, np.int8(2), k)
+                v = (best + em[t]).astype(np.float32)
+                bp[t] = k
+        s = S - 1
+        if S >= 2 and v[S - 2] > v[S - 1]:
+            s = S - 2
+        score[b] = v[s]
+        if not np.isfinite(v[s]):
+            if v[s] != ninf:                          # +inf / NaN out of infinities: report, no path
+                score[b] = v[s]
+            continue
+        for t in range(n - 1, -1, -1):
+            path[b, t] = cls[s]
+            if s & 1:
+                l = s >> 1
+                if tok_end[b, l] < 0:
+                    tok_end[b, l] = t
+                tok_start[b, l] = t
+            if t > 0:
+                s -= int(bp[t, s])
+        for l in range(L):
+            acc = np.float32(0.0)
+            for t in range(tok_start[b, l], tok_end[b, l] + 1):
+                acc = np.float32(acc + lp[t, lab[l]])
+            tok_score[b, l] = acc
+    return (torch.from_numpy(path), torch.from_numpy(tok_start), torch.from_numpy(tok_end),
+            torch.from_numpy(tok_score), torch.from_numpy(score))
