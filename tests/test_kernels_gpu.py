@@ -155,7 +155,8 @@ def test_ctc_fused(cuda, dtype):
 
 @pytest.mark.parametrize("Lmax,T", [(60, 150), (150, 241), (180, 400), (240, 500), (300, 700)])
 def test_ctc_long_labels(cuda, Lmax, T):
-    """Lattices of 121..601 states: every register-tile width of the one-wave recursion."""
+    """Lattices of 121..601 states: register-tile widths 4, 5, 6, 8 and 12 of the one-wave
+    recursion (widths 16 and 32, and full tiles: tests/test_ctc_gpu.py test_every_register_tile_width)."""
     from deepspeech_amd.ops import ctc as CTC
     torch.manual_seed(1)
     N, K = 5, 29
