@@ -36,10 +36,17 @@ int ds2_prep_inputs(const float* x, void* y, long long n, const int* lens_in, in
                     hipStream_t st);
 int ds2_transpose_bf16(const void* in, void* out, int R, int C, int ldi, int ldo, hipStream_t st);
 
+// ---- the recurrences ---------------------------------------------------------------------
+// Geometry every recurrence descriptor starts with, in the order ops/rnn.py _geom builds it
+// (generation 1 leaves R, xcd_map and knobs 0; the fp8 kernels are GRU only and take no knobs).
+struct DS2RnnGeom {
+  int T, N, NP, H, BG, R, steps, gstride, ndir, xcd_map, cell, knobs;
+};
+
 // ---- rnn_persistent.hip (and its timestamped build, rnn_persistent_stamps.hip) ------------
 // Python-visible descriptors (flat, fixed-layout structs filled by the bindings).
-struct DS2RnnFwd {
-  int T, N, NP, H, S, BG, steps, gstride, ndir, cell, nw, mt, persistent;
+struct DS2RnnFwd : DS2RnnGeom {
+  int S, nw, mt, persistent;
   const int* lens;
   const void* gx;
   const void* U[2];
@@ -54,8 +61,8 @@ struct DS2RnnFwd {
   unsigned long long* stamps;
 };
 
-struct DS2RnnBwd {
-  int T, N, NP, H, S, BG, steps, gstride, ndir, cell, nw, mt, persistent;
+struct DS2RnnBwd : DS2RnnGeom {
+  int S, nw, mt, persistent;
   const int* lens;
   const void* dy;
   const void* U[2];
@@ -81,8 +88,7 @@ int ds2_rnn_fwd_stamps(const DS2RnnFwd* d, hipStream_t st);
 int ds2_rnn_bwd_stamps(const DS2RnnBwd* d, hipStream_t st);
 
 // ---- rnn_xcd.hip ------------------------------------------------------------------------
-struct DS2RnnX {
-  int T, N, NP, H, BG, R, steps, gstride, ndir, cell, mt, xcd_map, knobs;
+struct DS2RnnX : DS2RnnGeom {
   const int* lens;
   const void* gx;        // fwd: gx;  bwd: dy
   const void* U[2];
@@ -105,15 +111,15 @@ struct DS2RnnX {
 
 int ds2_rnnx_fwd(const DS2RnnX* d, hipStream_t st);
 int ds2_rnnx_bwd_rs(const DS2RnnX* d, hipStream_t st);
-int ds2_rnnx_fwd_fuses_sum(int H, int cell, int mt, int ndir, int knobs);
-int ds2_rnnx_fwd_family(int H, int cell, int mt, int knobs);
-int ds2_rnnx_bwd_family(int H, int cell, int mt, int R);
+int ds2_rnnx_members(int H, int cell);
+int ds2_rnnx_fwd_fuses_sum(int H, int cell, int ndir, int knobs);
+int ds2_rnnx_fwd_family(int H, int cell, int knobs);
+int ds2_rnnx_bwd_family(int H, int cell, int R);
 long long ds2_rnnx_ring_floats(int H, int BG, int R);
 int ds2_rnnx_grid(int H, int cell, int ngroups, int xcd_map);
 
 // ---- rnn_fp8.hip ------------------------------------------------------------------------
-struct DS2RnnF8 {
-  int T, N, NP, H, BG, R, steps, gstride, ndir, xcd_map;
+struct DS2RnnF8 : DS2RnnGeom {
   const int* lens;
   const void* gx;
   const void* U8[2];
@@ -129,8 +135,7 @@ struct DS2RnnF8 {
   long long timeout;
 };
 
-struct DS2RnnF8B {
-  int T, N, NP, H, BG, R, steps, gstride, ndir, xcd_map;
+struct DS2RnnF8B : DS2RnnGeom {
   const int* lens;
   const void* dy;
   const void* U8T[2];

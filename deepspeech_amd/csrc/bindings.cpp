@@ -83,200 +83,233 @@ int is_bf16(const at::Tensor& t) {
   return 0;
 }
 
+void need_bf16(const at::Tensor& t, const char* name) {
+  need_gpu(t, name);
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " must be bf16");
+}
+void need_f32(const at::Tensor& t, const char* name, int64_t numel) {
+  need_gpu(t, name);
+  TORCH_CHECK(t.scalar_type() == at::kFloat, name, " must be float32");
+  TORCH_CHECK(t.numel() >= numel, name, " too small (", t.numel(), " < ", numel, ")");
+}
+int* need_i32(const at::Tensor& t, const char* name, int64_t numel) {
+  need_gpu(t, name);
+  TORCH_CHECK(t.scalar_type() == at::kInt, name, " must be int32");
+  TORCH_CHECK(t.numel() >= numel, name, " too small (", t.numel(), " < ", numel, ")");
+  return t.data_ptr<int>();
+}
+
 // --------------------------------------------------------------------------- RNN
-void rnn_fwd(at::Tensor gx, at::Tensor lens, at::Tensor U_f, OptT U_b, OptT bh_f, OptT bh_b, at::Tensor y_f,
-             OptT y_b, at::Tensor hx_f, OptT hx_b, at::Tensor hs_f, OptT hs_b, OptT gates_f, OptT gates_b,
-             at::Tensor flags, at::Tensor err, int64_t T, int64_t N, int64_t NP, int64_t H, int64_t BG, int64_t steps,
-             int64_t gstride, int64_t ndir, int64_t cell, int64_t nw, int64_t mt, bool persistent, int64_t timeout,
-             OptT stamps) {
-  need_gpu(gx, "gx");
-  TORCH_CHECK(gx.scalar_type() == at::kBFloat16, "gx must be bf16");
-  TORCH_CHECK(lens.scalar_type() == at::kInt, "lens must be int32");
-  TORCH_CHECK(gx.numel() >= T * N * gstride, "gx too small");
-  DS2RnnFwd d{};
-  d.T = (int)T; d.N = (int)N; d.NP = (int)NP; d.H = (int)H; d.S = (int)(H / 16); d.BG = (int)BG;
-  d.steps = (int)steps; d.gstride = (int)gstride; d.ndir = (int)ndir; d.cell = (int)cell; d.nw = (int)nw;
-  d.mt = (int)mt; d.persistent = persistent ? 1 : 0;
-  TORCH_CHECK(NP == BG * 16 * mt, "NP must equal BG*16*mt");
-  TORCH_CHECK(hx_f.numel() >= (steps + 1) * NP * H, "hx too small");
-  d.stamps = ptr_or_null<unsigned long long>(stamps, "stamps");
-  d.lens = lens.data_ptr<int>();
-  d.gx = gx.data_ptr();
-  d.U[0] = U_f.data_ptr();
-  d.U[1] = U_b.has_value() ? U_b->data_ptr() : nullptr;
-  d.bh[0] = ptr_or_null<const float>(bh_f, "bh_f");
-  d.bh[1] = ptr_or_null<const float>(bh_b, "bh_b");
-  d.y[0] = y_f.data_ptr();
-  d.y[1] = ptr_or_null<void>(y_b, "y_b");
-  d.hx[0] = hx_f.data_ptr();
-  d.hx[1] = ptr_or_null<void>(hx_b, "hx_b");
-  d.hsave[0] = hs_f.data_ptr<float>();
-  d.hsave[1] = ptr_or_null<float>(hs_b, "hsave_b");
-  d.gates[0] = ptr_or_null<float>(gates_f, "gates_f");
-  d.gates[1] = ptr_or_null<float>(gates_b, "gates_b");
-  TORCH_CHECK(ndir == 1 || (d.U[1] && d.y[1] && d.hx[1] && d.hsave[1]), "backward-direction buffers missing");
-  TORCH_CHECK(cell == 0 || (d.gates[0] && (ndir == 1 || d.gates[1])), "GRU needs gate buffers");
-  d.flags = reinterpret_cast<unsigned*>(flags.data_ptr<int>());
-  d.err = reinterpret_cast<unsigned*>(err.data_ptr<int>());
+// Every recurrence descriptor (csrc/api.h) is filled the same way: the geometry from the 12
+// integers of ops/rnn.py _geom, the buffers Python allocates stacked [ndir, ...] through
+// dir_ptrs, the bias partials through bias_parts. U and bh are separate arena parameters and
+// come as per-direction pairs (pair_ptrs).
+template <typename D>
+D rnn_desc(const std::vector<int64_t>& g, const at::Tensor& lens, const at::Tensor& err, int64_t timeout) {
+  TORCH_CHECK(g.size() == 12, "recurrence geometry: the 12 integers of ops/rnn.py _geom");
+  D d{};
+  static_cast<DS2RnnGeom&>(d) = DS2RnnGeom{(int)g[0], (int)g[1], (int)g[2], (int)g[3], (int)g[4],  (int)g[5],
+                                           (int)g[6], (int)g[7], (int)g[8], (int)g[9], (int)g[10], (int)g[11]};
+  TORCH_CHECK(d.T >= 0 && d.N >= 1 && d.NP >= d.N && d.BG >= 1 && d.H >= 32 && d.H % 32 == 0 && d.steps <= d.T &&
+                  (d.ndir == 1 || d.ndir == 2) && (d.cell == 0 || d.cell == 1),
+              "recurrence geometry out of range");
+  d.lens = need_i32(lens, "lens", d.N);
+  TORCH_CHECK(lens.numel() == d.N, "lens must be int32 [N]");
+  d.err = reinterpret_cast<unsigned*>(need_i32(err, "err", 1));
   d.timeout = timeout;
-  d.stamps = ptr_or_null<unsigned long long>(stamps, "stamps");
-  check(d.stamps ? ds2_rnn_fwd_stamps(&d, cur_stream()) : ds2_rnn_fwd(&d, cur_stream()), "rnn_fwd");
-}
-
-void rnn_bwd(at::Tensor dy, at::Tensor lens, at::Tensor U_f, OptT U_b, at::Tensor hs_f, OptT hs_b, OptT gates_f,
-             OptT gates_b, at::Tensor dgh_f, OptT dgh_b, at::Tensor dgx, OptT carry_f, OptT carry_b,
-             at::Tensor flags, at::Tensor err, int64_t T, int64_t N, int64_t NP, int64_t H, int64_t BG, int64_t steps,
-             int64_t gstride, int64_t ndir, int64_t cell, int64_t nw, int64_t mt, bool persistent, int64_t timeout,
-             OptT stamps, OptT dbx_part, OptT dbh_part, double dgx_scale) {
-  need_gpu(dy, "dy");
-  TORCH_CHECK(dy.scalar_type() == at::kBFloat16 && dgx.scalar_type() == at::kBFloat16, "dy/dgx must be bf16");
-  TORCH_CHECK(dgx.numel() >= T * N * gstride, "dgx too small");
-  DS2RnnBwd d{};
-  d.T = (int)T; d.N = (int)N; d.NP = (int)NP; d.H = (int)H; d.S = (int)(H / 16); d.BG = (int)BG;
-  d.steps = (int)steps; d.gstride = (int)gstride; d.ndir = (int)ndir; d.cell = (int)cell; d.nw = (int)nw;
-  d.mt = (int)mt; d.persistent = persistent ? 1 : 0;
-  TORCH_CHECK(NP == BG * 16 * mt, "NP must equal BG*16*mt");
-  d.lens = lens.data_ptr<int>();
-  d.dy = dy.data_ptr();
-  d.U[0] = U_f.data_ptr();
-  d.U[1] = U_b.has_value() ? U_b->data_ptr() : nullptr;
-  d.hsave[0] = hs_f.data_ptr<float>();
-  d.hsave[1] = ptr_or_null<float>(hs_b, "hsave_b");
-  d.gates[0] = ptr_or_null<float>(gates_f, "gates_f");
-  d.gates[1] = ptr_or_null<float>(gates_b, "gates_b");
-  d.dgh[0] = dgh_f.data_ptr();
-  d.dgh[1] = ptr_or_null<void>(dgh_b, "dgh_b");
-  d.dgx = dgx.data_ptr();
-  d.carry[0] = ptr_or_null<float>(carry_f, "carry_f");
-  d.carry[1] = ptr_or_null<float>(carry_b, "carry_b");
-  const int G = cell == 1 ? 3 : 1;
-  float* bx = ptr_or_null<float>(dbx_part, "dbx_part");
-  float* bh = ptr_or_null<float>(dbh_part, "dbh_part");
-  if (bx) TORCH_CHECK(dbx_part->numel() == ndir * BG * G * H && dbx_part->scalar_type() == at::kFloat, "dbx_part must be fp32 [ndir, BG, G*H]");
-  if (bh) TORCH_CHECK(dbh_part->numel() == ndir * BG * G * H && dbh_part->scalar_type() == at::kFloat, "dbh_part must be fp32 [ndir, BG, G*H]");
-  for (int i = 0; i < 2; ++i) {
-    d.dbx_part[i] = (bx && i < ndir) ? bx + (size_t)i * BG * G * H : nullptr;
-    d.dbh_part[i] = (bh && i < ndir) ? bh + (size_t)i * BG * G * H : nullptr;
-  }
-  d.dgx_scale = (float)dgx_scale;
-  TORCH_CHECK(ndir == 1 || (d.U[1] && d.hsave[1] && d.dgh[1]), "backward-direction buffers missing");
-  d.flags = reinterpret_cast<unsigned*>(flags.data_ptr<int>());
-  d.err = reinterpret_cast<unsigned*>(err.data_ptr<int>());
-  d.timeout = timeout;
-  d.stamps = ptr_or_null<unsigned long long>(stamps, "stamps");
-  check(d.stamps ? ds2_rnn_bwd_stamps(&d, cur_stream()) : ds2_rnn_bwd(&d, cur_stream()), "rnn_bwd");
-}
-
-int64_t rnn_kpw(int64_t H, int64_t G, int64_t nw, bool fwd) { return ds2_rnn_kpw((int)H, (int)G, (int)nw, fwd ? 1 : 0); }
-
-// ---- generation-2 recurrence (XCD-local groups, sentinel hand-off): csrc/rnn_xcd.hip
-DS2RnnX rnnx_desc(int64_t T, int64_t N, int64_t NP, int64_t H, int64_t BG, int64_t R, int64_t steps, int64_t gstride,
-                  int64_t ndir, int64_t cell, int64_t mt, at::Tensor census, at::Tensor err, int64_t timeout,
-                  int64_t xcd_map, int64_t knobs) {
-  TORCH_CHECK(H % 32 == 0, "H must be a multiple of 32");
-  TORCH_CHECK(NP == BG * R && R >= 1 && R <= 16 * mt && (mt == 1 || mt == 2), "bad row tiling");
-  const int64_t ngroups = ndir * BG;
-  TORCH_CHECK(census.numel() >= ngroups * (H / 32) && census.scalar_type() == at::kInt, "census too small");
-  need_gpu(census, "census");
-  DS2RnnX d{};
-  d.T = (int)T; d.N = (int)N; d.NP = (int)NP; d.H = (int)H; d.BG = (int)BG; d.R = (int)R; d.steps = (int)steps;
-  d.gstride = (int)gstride; d.ndir = (int)ndir; d.cell = (int)cell; d.mt = (int)mt;
-  d.xcd_map = (int)xcd_map; d.knobs = (int)knobs;
-  d.census = reinterpret_cast<unsigned*>(census.data_ptr<int>());
-  d.err = reinterpret_cast<unsigned*>(err.data_ptr<int>());
-  d.timeout = timeout;
-  d.dgx_scale = 1.f;
   return d;
 }
 
-void rnnx_fwd(at::Tensor gx, at::Tensor lens, at::Tensor U_f, OptT U_b, OptT bh_f, OptT bh_b, at::Tensor y_f,
-              OptT y_b, at::Tensor hx_f, OptT hx_b, at::Tensor hs_f, OptT hs_b, OptT gates_f, OptT gates_b,
-              at::Tensor census, at::Tensor err, int64_t T, int64_t N, int64_t NP, int64_t H, int64_t BG, int64_t R,
-              int64_t steps, int64_t gstride, int64_t ndir, int64_t cell, int64_t mt, int64_t timeout,
-              int64_t xcd_map, int64_t knobs, OptT stamps, OptT ysum) {
-  need_gpu(gx, "gx");
-  TORCH_CHECK(gx.scalar_type() == at::kBFloat16 && gx.numel() >= T * N * gstride, "gx must be bf16 [T, N, gstride]");
-  TORCH_CHECK(lens.scalar_type() == at::kInt && lens.numel() == N, "lens must be int32 [N]");
-  TORCH_CHECK(hx_f.numel() >= (steps + 1) * NP * H && hs_f.numel() >= (steps + 1) * NP * H, "state buffers too small");
-  DS2RnnX d = rnnx_desc(T, N, NP, H, BG, R, steps, gstride, ndir, cell, mt, census, err, timeout, xcd_map, knobs);
-  d.stamps = ptr_or_null<unsigned long long>(stamps, "stamps");
-  d.lens = lens.data_ptr<int>();
-  d.gx = gx.data_ptr();
-  d.U[0] = U_f.data_ptr();
-  d.U[1] = U_b.has_value() ? U_b->data_ptr() : nullptr;
-  d.bh[0] = ptr_or_null<const float>(bh_f, "bh_f");
-  d.bh[1] = ptr_or_null<const float>(bh_b, "bh_b");
-  d.y[0] = y_f.data_ptr();
-  d.y[1] = ptr_or_null<void>(y_b, "y_b");
-  d.ex[0] = hx_f.data_ptr();
-  d.ex[1] = ptr_or_null<void>(hx_b, "hx_b");
-  d.hsave[0] = hs_f.data_ptr<float>();
-  d.hsave[1] = ptr_or_null<float>(hs_b, "hs_b");
-  d.gates[0] = ptr_or_null<float>(gates_f, "gates_f");
-  d.gates[1] = ptr_or_null<float>(gates_b, "gates_b");
-  d.ysum = nullptr;
-  if (ysum.has_value()) {
-    TORCH_CHECK(ysum->scalar_type() == at::kBFloat16 && ysum->numel() >= T * N * H && ysum->is_contiguous(),
-                "ysum must be contiguous bf16 [T, N, H]");
-    d.ysum = ysum->data_ptr();
+// The direction pointers of a stacked buffer [ndir, per_dir elements]: on the device, of the
+// given dtype, contiguous, of exactly that size (at_least: or larger, for state a longer
+// launch saved; the directions then lie numel / ndir apart). Directions past ndir stay null.
+template <typename P>
+void dir_ptrs(P* (&out)[2], const at::Tensor& t, const char* name, at::ScalarType dtype, int64_t ndir,
+              int64_t per_dir, bool at_least = false) {
+  need_gpu(t, name);
+  const int64_t n = t.numel();
+  TORCH_CHECK(t.scalar_type() == dtype && (at_least ? n >= ndir * per_dir && n % ndir == 0 : n == ndir * per_dir),
+              name, " must be ", dtype, " [", ndir, ", ", per_dir, at_least ? " or more]" : "]", ", got ", n, " of ",
+              t.scalar_type());
+  char* base = static_cast<char*>(t.data_ptr());
+  for (int i = 0; i < 2; ++i) out[i] = i < ndir ? reinterpret_cast<P*>(base + i * (n / ndir) * t.element_size()) : nullptr;
+}
+template <typename P>
+void dir_ptrs(P* (&out)[2], const OptT& t, const char* name, at::ScalarType dtype, int64_t ndir, int64_t per_dir,
+              bool at_least = false) {
+  out[0] = out[1] = nullptr;
+  if (t.has_value() && t->defined()) dir_ptrs(out, *t, name, dtype, ndir, per_dir, at_least);
+}
+
+// Bias-gradient partials fp32 [k, ndir, BG, G*H] (k = 0 the input bias, k = 1 the GRU's
+// recurrent bias) or none: per_dir = BG * G * H
+void bias_parts(float* (&bx)[2], float* (&bh)[2], const OptT& parts, int64_t k, int64_t ndir, int64_t per_dir) {
+  float* by_k[2];
+  dir_ptrs(by_k, parts, "bias partials", at::kFloat, k, ndir * per_dir);
+  for (int i = 0; i < 2; ++i) {
+    bx[i] = (by_k[0] && i < ndir) ? by_k[0] + i * per_dir : nullptr;
+    bh[i] = (by_k[1] && i < ndir) ? by_k[1] + i * per_dir : nullptr;
   }
-  TORCH_CHECK(ndir == 1 || (d.U[1] && d.y[1] && d.ex[1] && d.hsave[1]), "backward-direction buffers missing");
-  TORCH_CHECK(cell == 0 || (d.gates[0] && (ndir == 1 || d.gates[1])), "GRU needs gate buffers");
+}
+
+template <typename P>
+void pair_ptrs(P* (&out)[2], const OptT& f, const OptT& b, const char* name, int ndir, bool required) {
+  out[0] = ptr_or_null<P>(f, name);
+  out[1] = ndir == 2 ? ptr_or_null<P>(b, name) : nullptr;
+  TORCH_CHECK(!required || (out[0] && (ndir == 1 || out[1])), name, ": a direction's tensor is missing");
+}
+
+// bf16 [T, N, row] activations / gradients beside the recurrence: gx, dy, dgx
+void* need_seq(const at::Tensor& t, const char* name, const DS2RnnGeom& d, int64_t row, bool exact = false) {
+  need_bf16(t, name);
+  const int64_t n = (int64_t)d.T * d.N * row;
+  TORCH_CHECK(exact ? t.numel() == n : t.numel() >= n, name, " must be bf16 [T, N, ", row, "]");
+  return t.data_ptr();
+}
+
+// ---- generation 1 (csrc/rnn_persistent.hip): 16*mt-row tiles, one flag word per workgroup
+template <typename D>
+D rnn1_desc(const std::vector<int64_t>& g, const at::Tensor& lens, const at::Tensor& err, int64_t timeout, int64_t nw,
+            int64_t mt, bool persistent, const at::Tensor& flags, const OptT& stamps) {
+  D d = rnn_desc<D>(g, lens, err, timeout);
+  TORCH_CHECK(d.NP == d.BG * 16 * mt, "NP must equal BG*16*mt");
+  d.S = d.H / 16; d.nw = (int)nw; d.mt = (int)mt; d.persistent = persistent ? 1 : 0;
+  d.flags = reinterpret_cast<unsigned*>(need_i32(flags, "flags", (int64_t)d.ndir * d.BG * d.S));
+  d.stamps = ptr_or_null<unsigned long long>(stamps, "stamps");
+  return d;
+}
+
+void rnn_fwd(std::vector<int64_t> geom, int64_t nw, int64_t mt, bool persistent, at::Tensor gx, at::Tensor lens,
+             OptT U_f, OptT U_b, OptT bh_f, OptT bh_b, at::Tensor y, at::Tensor hx, at::Tensor hs, OptT gates,
+             at::Tensor flags, at::Tensor err, int64_t timeout, OptT stamps) {
+  DS2RnnFwd d = rnn1_desc<DS2RnnFwd>(geom, lens, err, timeout, nw, mt, persistent, flags, stamps);
+  const int64_t hsz = (int64_t)(d.steps + 1) * d.NP * d.H;
+  d.gx = need_seq(gx, "gx", d, d.gstride);
+  pair_ptrs(d.U, U_f, U_b, "U", d.ndir, true);
+  pair_ptrs(d.bh, bh_f, bh_b, "bh", d.ndir, false);
+  dir_ptrs(d.y, y, "y", at::kBFloat16, d.ndir, (int64_t)d.T * d.N * d.H);
+  dir_ptrs(d.hx, hx, "hx", at::kBFloat16, d.ndir, hsz, true);
+  dir_ptrs(d.hsave, hs, "hs", at::kFloat, d.ndir, hsz, true);
+  dir_ptrs(d.gates, gates, "gates", at::kFloat, d.ndir, (int64_t)d.steps * d.NP * d.H * 4, true);
+  TORCH_CHECK(d.cell == 0 || d.gates[0], "GRU needs gate buffers");
+  check(d.stamps ? ds2_rnn_fwd_stamps(&d, cur_stream()) : ds2_rnn_fwd(&d, cur_stream()), "rnn_fwd");
+}
+
+void rnn_bwd(std::vector<int64_t> geom, int64_t nw, int64_t mt, bool persistent, at::Tensor dy, at::Tensor lens,
+             OptT U_f, OptT U_b, at::Tensor hs, OptT gates, at::Tensor dgh, at::Tensor dgx, OptT carry, OptT parts,
+             double dgx_scale, at::Tensor flags, at::Tensor err, int64_t timeout, OptT stamps) {
+  DS2RnnBwd d = rnn1_desc<DS2RnnBwd>(geom, lens, err, timeout, nw, mt, persistent, flags, stamps);
+  const int64_t G = d.cell == 1 ? 3 : 1;
+  d.dy = need_seq(dy, "dy", d, d.H);
+  d.dgx = need_seq(dgx, "dgx", d, d.gstride);
+  d.dgx_scale = (float)dgx_scale;
+  pair_ptrs(d.U, U_f, U_b, "U", d.ndir, true);
+  dir_ptrs(d.hsave, hs, "hs", at::kFloat, d.ndir, (int64_t)(d.steps + 1) * d.NP * d.H, true);
+  dir_ptrs(d.gates, gates, "gates", at::kFloat, d.ndir, (int64_t)d.steps * d.NP * d.H * 4, true);
+  TORCH_CHECK(d.cell == 0 || d.gates[0], "GRU needs gate buffers");
+  dir_ptrs(d.dgh, dgh, "dgh", at::kBFloat16, d.ndir, (int64_t)d.steps * d.NP * G * d.H);
+  dir_ptrs(d.carry, carry, "carry", at::kFloat, d.ndir, (int64_t)d.NP * d.H);
+  bias_parts(d.dbx_part, d.dbh_part, parts, d.cell == 1 ? 2 : 1, d.ndir, d.BG * G * d.H);
+  check(d.stamps ? ds2_rnn_bwd_stamps(&d, cur_stream()) : ds2_rnn_bwd(&d, cur_stream()), "rnn_bwd");
+}
+
+// ---- XCD-local groups of R rows (csrc/rnn_xcd.hip: 32 units per census word, R <= 16;
+// csrc/rnn_fp8.hip: 64 units, R <= 8)
+template <typename D>
+D rnnx_desc(const std::vector<int64_t>& g, const at::Tensor& lens, const at::Tensor& err, int64_t timeout,
+            const at::Tensor& census, int units, int max_rows) {
+  D d = rnn_desc<D>(g, lens, err, timeout);
+  TORCH_CHECK(d.NP == d.BG * d.R && d.R >= 1 && d.R <= max_rows, "bad row tiling");
+  d.census = reinterpret_cast<unsigned*>(need_i32(census, "census", (int64_t)d.ndir * d.BG * (d.H / units)));
+  return d;
+}
+
+void rnnx_fwd(std::vector<int64_t> geom, at::Tensor gx, at::Tensor lens, OptT U_f, OptT U_b, OptT bh_f, OptT bh_b,
+              OptT y, OptT ysum, at::Tensor hx, at::Tensor hs, OptT gates, at::Tensor census, at::Tensor err,
+              int64_t timeout, OptT stamps) {
+  DS2RnnX d = rnnx_desc<DS2RnnX>(geom, lens, err, timeout, census, 32, 16);
+  const int64_t hsz = (int64_t)(d.steps + 1) * d.NP * d.H;
+  d.gx = need_seq(gx, "gx", d, d.gstride);
+  d.dgx_scale = 1.f;
+  pair_ptrs(d.U, U_f, U_b, "U", d.ndir, true);
+  pair_ptrs(d.bh, bh_f, bh_b, "bh", d.ndir, false);
+  // the fused direction sum (generations 4 - 6) is both directions' output
+  if (ysum.has_value()) d.y[0] = d.y[1] = d.ysum = need_seq(*ysum, "ysum", d, d.H);
+  else dir_ptrs(d.y, y, "y", at::kBFloat16, d.ndir, (int64_t)d.T * d.N * d.H);
+  TORCH_CHECK(d.y[0], "rnnx_fwd needs y or ysum");
+  dir_ptrs(d.ex, hx, "hx", at::kBFloat16, d.ndir, hsz, true);
+  dir_ptrs(d.hsave, hs, "hs", at::kFloat, d.ndir, hsz, true);
+  dir_ptrs(d.gates, gates, "gates", at::kFloat, d.ndir, (int64_t)d.steps * d.NP * d.H * 4, true);
+  TORCH_CHECK(d.cell == 0 || d.gates[0], "GRU needs gate buffers");
+  d.stamps = ptr_or_null<unsigned long long>(stamps, "stamps");
   check(ds2_rnnx_fwd(&d, cur_stream()), "rnnx_fwd");
 }
 
-// csrc/rnn_fp8.hip: GRU forward with e4m3 U (per-tensor power-of-two scale, uexp = E8M0 exponent
-// per direction on the device) and an e4m3 hidden-state exchange hq [ndir][steps+1][NP][H]
-// (slot 0 = e4m3 h0, slots 1.. 0xFF); saves hs / gates / bf16 hx like rnnx_fwd.
-void rnnf8_fwd(at::Tensor gx, at::Tensor lens, at::Tensor U8, at::Tensor uexp, OptT bh_f, OptT bh_b, at::Tensor y,
-               at::Tensor hq, at::Tensor hx, at::Tensor hs, at::Tensor gates, at::Tensor census, at::Tensor err,
-               int64_t T, int64_t N, int64_t NP, int64_t H, int64_t BG, int64_t R, int64_t steps, int64_t gstride,
-               int64_t ndir, int64_t timeout, int64_t xcd_map) {
-  need_gpu(gx, "gx");
-  TORCH_CHECK(gx.scalar_type() == at::kBFloat16 && gx.is_contiguous() && gx.numel() >= T * N * gstride,
-              "gx must be contiguous bf16 [T, N, gstride]");
-  TORCH_CHECK(gstride >= ndir * 3 * H, "gstride");
-  TORCH_CHECK(lens.scalar_type() == at::kInt && lens.numel() == N, "lens must be int32 [N]");
-  TORCH_CHECK(U8.scalar_type() == at::kByte && U8.is_contiguous() && U8.numel() == ndir * 3 * H * H,
-              "U8 must be uint8 [ndir, 3H, H]");
-  TORCH_CHECK(uexp.scalar_type() == at::kInt && uexp.numel() >= ndir, "uexp must be int32 [ndir]");
-  TORCH_CHECK(y.scalar_type() == at::kBFloat16 && y.is_contiguous() && y.numel() == ndir * T * N * H, "y [ndir,T,N,H]");
-  TORCH_CHECK(hq.scalar_type() == at::kByte && hq.is_contiguous() && hq.numel() == ndir * (steps + 1) * NP * H,
-              "hq must be uint8 [ndir, steps+1, NP, H]");
-  TORCH_CHECK(hx.scalar_type() == at::kBFloat16 && hx.is_contiguous() && hx.numel() == ndir * (steps + 1) * NP * H,
-              "hx must be bf16 [ndir, steps+1, NP, H]");
-  TORCH_CHECK(hs.scalar_type() == at::kFloat && hs.is_contiguous() && hs.numel() == ndir * (steps + 1) * NP * H,
-              "hs must be fp32 [ndir, steps+1, NP, H]");
-  TORCH_CHECK(gates.scalar_type() == at::kFloat && gates.is_contiguous() && gates.numel() == ndir * steps * NP * H * 4,
-              "gates must be fp32 [ndir, steps, NP, H, 4]");
-  TORCH_CHECK(census.scalar_type() == at::kInt && census.numel() >= ndir * BG * (H / 64), "census too small");
-  TORCH_CHECK(ds2_rnnf8_supported((int)H, (int)N, (int)ndir), "rnnf8: unsupported geometry");
-  TORCH_CHECK(steps >= 1 && steps <= T && R >= 1 && R <= 8 && NP == BG * R && BG * ndir <= 8, "rnnf8: plan");
-  for (const at::Tensor* t : {&U8, &y, &hq, &hx, &hs, &gates, &census, &err, &lens, &uexp}) need_gpu(*t, "rnnf8 operand");
-  DS2RnnF8 d;
-  d.T = (int)T; d.N = (int)N; d.NP = (int)NP; d.H = (int)H; d.BG = (int)BG; d.R = (int)R; d.steps = (int)steps;
-  d.gstride = (int)gstride; d.ndir = (int)ndir; d.xcd_map = (int)xcd_map;
-  d.lens = lens.data_ptr<int>();
-  d.gx = gx.data_ptr();
-  const size_t usz = (size_t)3 * H * H, hsz = (size_t)(steps + 1) * NP * H;
-  const size_t ysz = (size_t)T * N * H, gsz = (size_t)steps * NP * H * 4;
-  for (int i = 0; i < 2; ++i) {
-    const bool on = i < ndir;
-    d.U8[i] = on ? (const void*)(U8.data_ptr<uint8_t>() + i * usz) : nullptr;
-    d.y[i] = on ? (void*)(reinterpret_cast<uint16_t*>(y.data_ptr()) + i * ysz) : nullptr;
-    d.hq[i] = on ? (void*)(hq.data_ptr<uint8_t>() + i * hsz) : nullptr;
-    d.hx[i] = on ? (void*)(reinterpret_cast<uint16_t*>(hx.data_ptr()) + i * hsz) : nullptr;
-    d.hsave[i] = on ? hs.data_ptr<float>() + i * hsz : nullptr;
-    d.gates[i] = on ? gates.data_ptr<float>() + i * gsz : nullptr;
-  }
-  d.uexp = uexp.data_ptr<int>();
-  d.bh[0] = ptr_or_null<const float>(bh_f, "bh_f");
-  d.bh[1] = ptr_or_null<const float>(bh_b, "bh_b");
-  d.census = reinterpret_cast<unsigned*>(census.data_ptr<int>());
-  d.err = reinterpret_cast<unsigned*>(err.data_ptr<int>());
-  d.timeout = timeout;
+// reduce-scatter BPTT (generation 3): dgh is a plain output, the exchange is the fp32 ring
+// [ndir, ds2_rnnx_ring_floats], sentinel-filled
+void rnnx_bwd(std::vector<int64_t> geom, at::Tensor dy, at::Tensor lens, OptT U_f, OptT U_b, at::Tensor hs, OptT gates,
+              at::Tensor dgh, at::Tensor dgx, OptT parts, double dgx_scale, at::Tensor census, at::Tensor err,
+              at::Tensor ring, int64_t timeout, OptT stamps) {
+  DS2RnnX d = rnnx_desc<DS2RnnX>(geom, lens, err, timeout, census, 32, 16);
+  const int64_t G = d.cell == 1 ? 3 : 1;
+  d.gx = need_seq(dy, "dy", d, d.H);
+  d.dgx = need_seq(dgx, "dgx", d, d.gstride);
+  d.dgx_scale = (float)dgx_scale;
+  pair_ptrs(d.U, U_f, U_b, "U", d.ndir, true);
+  dir_ptrs(d.hsave, hs, "hs", at::kFloat, d.ndir, (int64_t)(d.steps + 1) * d.NP * d.H, true);
+  dir_ptrs(d.gates, gates, "gates", at::kFloat, d.ndir, (int64_t)d.steps * d.NP * d.H * 4, true);
+  TORCH_CHECK(d.cell == 0 || d.gates[0], "GRU needs gate buffers");
+  dir_ptrs(d.ex, dgh, "dgh", at::kBFloat16, d.ndir, (int64_t)d.steps * d.NP * G * d.H, true);
+  dir_ptrs(d.ring, ring, "ring", at::kFloat, d.ndir, ds2_rnnx_ring_floats(d.H, d.BG, d.R), true);
+  bias_parts(d.dbx_part, d.dbh_part, parts, d.cell == 1 ? 2 : 1, d.ndir, d.BG * G * d.H);
+  d.stamps = ptr_or_null<unsigned long long>(stamps, "stamps");
+  check(ds2_rnnx_bwd_rs(&d, cur_stream()), "rnnx_bwd_rs");
+}
+
+// csrc/rnn_fp8.hip: GRU forward with e4m3 U8 [ndir, 3H, H] (per-tensor power-of-two scale, uexp =
+// E8M0 exponent per direction on the device) and an e4m3 hidden-state exchange hq [ndir][steps+1]
+// [NP][H] (slot 0 = e4m3 h0, slots 1.. 0xFF); saves hs / gates / bf16 hx like rnnx_fwd.
+void rnnf8_fwd(std::vector<int64_t> geom, at::Tensor gx, at::Tensor lens, at::Tensor U8, at::Tensor uexp, OptT bh_f,
+               OptT bh_b, at::Tensor y, at::Tensor hq, at::Tensor hx, at::Tensor hs, at::Tensor gates,
+               at::Tensor census, at::Tensor err, int64_t timeout) {
+  DS2RnnF8 d = rnnx_desc<DS2RnnF8>(geom, lens, err, timeout, census, 64, 8);
+  TORCH_CHECK(ds2_rnnf8_supported(d.H, d.N, d.ndir), "rnnf8: unsupported geometry");
+  TORCH_CHECK(d.steps >= 1 && d.BG * d.ndir <= 8 && d.gstride >= d.ndir * 3 * d.H, "rnnf8: plan");
+  const int64_t hsz = (int64_t)(d.steps + 1) * d.NP * d.H;
+  d.gx = need_seq(gx, "gx", d, d.gstride);
+  dir_ptrs(d.U8, U8, "U8", at::kByte, d.ndir, (int64_t)3 * d.H * d.H);
+  d.uexp = need_i32(uexp, "uexp", d.ndir);
+  pair_ptrs(d.bh, bh_f, bh_b, "bh", d.ndir, false);
+  dir_ptrs(d.y, y, "y", at::kBFloat16, d.ndir, (int64_t)d.T * d.N * d.H);
+  dir_ptrs(d.hq, hq, "hq", at::kByte, d.ndir, hsz);
+  dir_ptrs(d.hx, hx, "hx", at::kBFloat16, d.ndir, hsz);
+  dir_ptrs(d.hsave, hs, "hs", at::kFloat, d.ndir, hsz);
+  dir_ptrs(d.gates, gates, "gates", at::kFloat, d.ndir, (int64_t)d.steps * d.NP * d.H * 4);
   check(ds2_rnnf8_fwd(&d, cur_stream()), "rnnf8_fwd");
 }
+
+// csrc/rnn_fp8.hip fp8 GRU BPTT: U8T [ndir, H, 3H] e4m3 U^T (uexp per direction), saved fp32
+// h / gates of the forward, tagged-bf16 reduce-scatter ring [ndir, ring_words] filled 0xFF..
+void rnnf8_bwd(std::vector<int64_t> geom, at::Tensor dy, at::Tensor lens, at::Tensor U8T, at::Tensor uexp,
+               at::Tensor hs, at::Tensor gates, at::Tensor dgh, at::Tensor dgx, OptT parts, double dgx_scale,
+               at::Tensor census, at::Tensor err, at::Tensor ring, int64_t timeout) {
+  DS2RnnF8B d = rnnx_desc<DS2RnnF8B>(geom, lens, err, timeout, census, 64, 8);
+  TORCH_CHECK(ds2_rnnf8_bwd_supported(d.H, d.N, d.ndir), "rnnf8_bwd: unsupported geometry");
+  TORCH_CHECK(d.steps >= 1 && d.BG * d.ndir <= 8 && d.gstride >= d.ndir * 3 * d.H, "rnnf8_bwd: plan");
+  d.dy = need_seq(dy, "dy", d, d.H, true);
+  d.dgx = need_seq(dgx, "dgx", d, d.gstride, true);
+  d.dgx_scale = (float)dgx_scale;
+  dir_ptrs(d.U8T, U8T, "U8T", at::kByte, d.ndir, (int64_t)3 * d.H * d.H);
+  d.uexp = need_i32(uexp, "uexp", d.ndir);
+  dir_ptrs(d.hsave, hs, "hs", at::kFloat, d.ndir, (int64_t)(d.steps + 1) * d.NP * d.H, true);
+  dir_ptrs(d.gates, gates, "gates", at::kFloat, d.ndir, (int64_t)d.steps * d.NP * d.H * 4, true);
+  dir_ptrs(d.dgh, dgh, "dgh", at::kBFloat16, d.ndir, (int64_t)d.steps * d.NP * 3 * d.H);
+  dir_ptrs(d.ring, ring, "ring", at::kInt, d.ndir, ds2_rnnf8_ring_words(d.H, d.BG, d.R), true);
+  bias_parts(d.dbx_part, d.dbh_part, parts, 2, d.ndir, (int64_t)d.BG * 3 * d.H);
+  check(ds2_rnnf8_bwd(&d, cur_stream()), "rnnf8_bwd");
+}
+
+int64_t rnn_kpw(int64_t H, int64_t G, int64_t nw, bool fwd) { return ds2_rnn_kpw((int)H, (int)G, (int)nw, fwd ? 1 : 0); }
 
 // e4m3 copy of a bf16 tensor scaled by ONE power of two (amax / 2^e <= 448); uexp[0] = 127 + e
 void fp8_quant_pow2(at::Tensor x, at::Tensor q, at::Tensor uexp, at::Tensor amax) {
@@ -335,115 +368,6 @@ void fp8_quant_pow2_t(at::Tensor x, at::Tensor q, at::Tensor uexp, at::Tensor am
   check(ds2_fp8_quant_pow2_t(x.data_ptr(), (int)x.size(0), (int)x.size(1), q.data_ptr(), uexp.data_ptr<int>(),
                              reinterpret_cast<unsigned*>(amax.data_ptr<int>()), cur_stream()),
         "fp8_quant_pow2_t");
-}
-
-// csrc/rnn_fp8.hip fp8 GRU BPTT: U8T [ndir, H, 3H] e4m3 U^T (uexp per direction), saved fp32
-// h / gates of the forward, tagged-bf16 reduce-scatter ring [ndir, ring_words] filled 0xFF..
-void rnnf8_bwd(at::Tensor dy, at::Tensor lens, at::Tensor U8T, at::Tensor uexp, at::Tensor hs, at::Tensor gates,
-               at::Tensor dgh, at::Tensor dgx, OptT dbx_part, OptT dbh_part, double dgx_scale, at::Tensor census,
-               at::Tensor err, at::Tensor ring, int64_t T, int64_t N, int64_t NP, int64_t H, int64_t BG, int64_t R,
-               int64_t steps, int64_t gstride, int64_t ndir, int64_t timeout, int64_t xcd_map) {
-  need_gpu(dy, "dy");
-  TORCH_CHECK(ds2_rnnf8_bwd_supported((int)H, (int)N, (int)ndir), "rnnf8_bwd: unsupported geometry");
-  TORCH_CHECK(steps >= 1 && steps <= T && R >= 1 && R <= 8 && NP == BG * R && BG * ndir <= 8, "rnnf8_bwd: plan");
-  TORCH_CHECK(dy.scalar_type() == at::kBFloat16 && dy.is_contiguous() && dy.numel() == T * N * H, "dy bf16 [T,N,H]");
-  TORCH_CHECK(lens.scalar_type() == at::kInt && lens.numel() == N, "lens must be int32 [N]");
-  TORCH_CHECK(U8T.scalar_type() == at::kByte && U8T.is_contiguous() && U8T.numel() == ndir * 3 * H * H,
-              "U8T must be uint8 [ndir, H, 3H]");
-  TORCH_CHECK(uexp.scalar_type() == at::kInt && uexp.numel() >= ndir, "uexp must be int32 [ndir]");
-  TORCH_CHECK(hs.scalar_type() == at::kFloat && hs.is_contiguous() && hs.numel() >= ndir * (steps + 1) * NP * H &&
-                  hs.numel() % ndir == 0, "hs fp32 [ndir, >= steps+1, NP, H]");
-  TORCH_CHECK(gates.scalar_type() == at::kFloat && gates.is_contiguous() && gates.numel() >= ndir * steps * NP * H * 4 &&
-                  gates.numel() % ndir == 0, "gates fp32 [ndir, >= steps, NP, H, 4]");
-  TORCH_CHECK(dgh.scalar_type() == at::kBFloat16 && dgh.is_contiguous() && dgh.numel() == ndir * steps * NP * 3 * H,
-              "dgh bf16 [ndir, steps, NP, 3H]");
-  TORCH_CHECK(dgx.scalar_type() == at::kBFloat16 && dgx.is_contiguous() && dgx.numel() == T * N * gstride &&
-                  gstride >= ndir * 3 * H, "dgx bf16 [T, N, gstride]");
-  const long long rw = ds2_rnnf8_ring_words((int)H, (int)BG, (int)R);
-  TORCH_CHECK(ring.scalar_type() == at::kInt && ring.is_contiguous() && ring.numel() >= ndir * rw, "ring too small");
-  TORCH_CHECK(census.scalar_type() == at::kInt && census.numel() >= ndir * BG * (H / 64), "census too small");
-  for (const OptT* o : {&dbx_part, &dbh_part})
-    if (o->has_value() && (*o)->defined())
-      TORCH_CHECK((*o)->scalar_type() == at::kFloat && (*o)->is_contiguous() && (*o)->numel() == ndir * BG * 3 * H,
-                  "bias partials fp32 [ndir, BG, 3H]");
-  for (const at::Tensor* t : {&U8T, &hs, &gates, &dgh, &dgx, &census, &err, &lens, &uexp, &ring}) need_gpu(*t, "rnnf8_bwd operand");
-  DS2RnnF8B d;
-  d.T = (int)T; d.N = (int)N; d.NP = (int)NP; d.H = (int)H; d.BG = (int)BG; d.R = (int)R; d.steps = (int)steps;
-  d.gstride = (int)gstride; d.ndir = (int)ndir; d.xcd_map = (int)xcd_map;
-  d.lens = lens.data_ptr<int>();
-  d.dy = dy.data_ptr();
-  const size_t usz = (size_t)3 * H * H, hsz = hs.numel() / ndir, gsz = gates.numel() / ndir;
-  const size_t dsz = (size_t)steps * NP * 3 * H, bsz = (size_t)BG * 3 * H;
-  float* bx = ptr_or_null<float>(dbx_part, "dbx_part");
-  float* bh = ptr_or_null<float>(dbh_part, "dbh_part");
-  for (int i = 0; i < 2; ++i) {
-    const bool on = i < ndir;
-    d.U8T[i] = on ? (const void*)(U8T.data_ptr<uint8_t>() + i * usz) : nullptr;
-    d.hsave[i] = on ? hs.data_ptr<float>() + i * hsz : nullptr;
-    d.gates[i] = on ? gates.data_ptr<float>() + i * gsz : nullptr;
-    d.dgh[i] = on ? (void*)(reinterpret_cast<uint16_t*>(dgh.data_ptr()) + i * dsz) : nullptr;
-    d.ring[i] = on ? (void*)(ring.data_ptr<int>() + i * rw) : nullptr;
-    d.dbx_part[i] = (on && bx) ? bx + i * bsz : nullptr;
-    d.dbh_part[i] = (on && bh) ? bh + i * bsz : nullptr;
-  }
-  d.dgx = dgx.data_ptr();
-  d.uexp = uexp.data_ptr<int>();
-  d.dgx_scale = (float)dgx_scale;
-  d.census = reinterpret_cast<unsigned*>(census.data_ptr<int>());
-  d.err = reinterpret_cast<unsigned*>(err.data_ptr<int>());
-  d.timeout = timeout;
-  check(ds2_rnnf8_bwd(&d, cur_stream()), "rnnf8_bwd");
-}
-
-void rnnx_bwd(at::Tensor dy, at::Tensor lens, at::Tensor U_f, OptT U_b, at::Tensor hs_f, OptT hs_b, OptT gates_f,
-              OptT gates_b, at::Tensor dgh_f, OptT dgh_b, at::Tensor dgx, OptT dbx_part, OptT dbh_part,
-              double dgx_scale, at::Tensor census, at::Tensor err, int64_t T, int64_t N, int64_t NP, int64_t H,
-              int64_t BG, int64_t R, int64_t steps, int64_t gstride, int64_t ndir, int64_t cell, int64_t mt,
-              int64_t timeout, int64_t xcd_map, int64_t knobs, OptT stamps, OptT ring_f, OptT ring_b) {
-  need_gpu(dy, "dy");
-  TORCH_CHECK(dy.scalar_type() == at::kBFloat16 && dgx.scalar_type() == at::kBFloat16, "dy/dgx must be bf16");
-  TORCH_CHECK(dgx.numel() >= T * N * gstride && dy.numel() >= T * N * H, "dy/dgx too small");
-  const int64_t G = cell == 1 ? 3 : 1;
-  TORCH_CHECK(dgh_f.numel() >= steps * NP * G * H, "dgh too small");
-  DS2RnnX d = rnnx_desc(T, N, NP, H, BG, R, steps, gstride, ndir, cell, mt, census, err, timeout, xcd_map, knobs);
-  d.stamps = ptr_or_null<unsigned long long>(stamps, "stamps");
-  d.lens = lens.data_ptr<int>();
-  d.gx = dy.data_ptr();
-  d.U[0] = U_f.data_ptr();
-  d.U[1] = U_b.has_value() ? U_b->data_ptr() : nullptr;
-  d.hsave[0] = hs_f.data_ptr<float>();
-  d.hsave[1] = ptr_or_null<float>(hs_b, "hs_b");
-  d.gates[0] = ptr_or_null<float>(gates_f, "gates_f");
-  d.gates[1] = ptr_or_null<float>(gates_b, "gates_b");
-  d.ex[0] = dgh_f.data_ptr();
-  d.ex[1] = ptr_or_null<void>(dgh_b, "dgh_b");
-  d.dgx = dgx.data_ptr();
-  float* bx = ptr_or_null<float>(dbx_part, "dbx_part");
-  float* bh = ptr_or_null<float>(dbh_part, "dbh_part");
-  if (bx) TORCH_CHECK(dbx_part->numel() == ndir * BG * G * H && dbx_part->scalar_type() == at::kFloat, "dbx_part must be fp32 [ndir, BG, G*H]");
-  if (bh) TORCH_CHECK(dbh_part->numel() == ndir * BG * G * H && dbh_part->scalar_type() == at::kFloat, "dbh_part must be fp32 [ndir, BG, G*H]");
-  for (int i = 0; i < 2; ++i) {
-    d.dbx_part[i] = (bx && i < ndir) ? bx + (size_t)i * BG * G * H : nullptr;
-    d.dbh_part[i] = (bh && i < ndir) ? bh + (size_t)i * BG * G * H : nullptr;
-  }
-  d.dgx_scale = (float)dgx_scale;
-  TORCH_CHECK(ndir == 1 || (d.U[1] && d.hsave[1] && d.ex[1]), "backward-direction buffers missing");
-  // reduce-scatter BPTT (generation 3): dgh is a plain output, the exchange is the ring
-  TORCH_CHECK(ring_f.has_value() && ring_f->defined(), "rnnx_bwd needs the reduce-scatter ring");
-  const int64_t rf = ds2_rnnx_ring_floats((int)H, (int)BG, (int)R);
-  TORCH_CHECK(ring_f->scalar_type() == at::kFloat && ring_f->numel() >= rf, "ring_f must be fp32 [", rf, "]");
-  d.ring[0] = ring_f->data_ptr();
-  if (ndir == 2) {
-    TORCH_CHECK(ring_b.has_value() && ring_b->scalar_type() == at::kFloat && ring_b->numel() >= rf, "ring_b missing");
-    d.ring[1] = ring_b->data_ptr();
-  }
-  check(ds2_rnnx_bwd_rs(&d, cur_stream()), "rnnx_bwd_rs");
-}
-
-py::dict rnnx_info(int64_t H, int64_t G, int64_t ngroups, int64_t xcd_map) {
-  py::dict d;
-  d["grid"] = ds2_rnnx_grid((int)H, G == 3 ? 1 : 0, (int)ngroups, (int)xcd_map);
-  return d;
 }
 
 // --------------------------------------------------------------------------- CTC
@@ -607,16 +531,6 @@ void cast_bf16(at::Tensor x, at::Tensor y) {
 }
 
 // --------------------------------------------------------------------------- conv front-end
-void need_bf16(const at::Tensor& t, const char* name) {
-  need_gpu(t, name);
-  TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " must be bf16");
-}
-void need_f32(const at::Tensor& t, const char* name, int64_t numel) {
-  need_gpu(t, name);
-  TORCH_CHECK(t.scalar_type() == at::kFloat, name, " must be float32");
-  TORCH_CHECK(t.numel() >= numel, name, " too small (", t.numel(), " < ", numel, ")");
-}
-
 // x [N,T,F0] bf16, w [32,1,20,5] bf16 -> y [N,T1,F1,32] bf16, part [grid, 64] f32
 void conv1_fwd(at::Tensor x, at::Tensor w, OptT bias, at::Tensor y, at::Tensor part) {
   need_bf16(x, "x"); need_bf16(w, "w"); need_bf16(y, "y");
@@ -1396,19 +1310,8 @@ py::dict device_info(int64_t dev) {
 
 PYBIND11_MODULE(_C, m) {
   m.doc() = "deepspeech_amd gfx950 kernels";
-  m.def("rnn_fwd", &rnn_fwd, py::arg("gx"), py::arg("lens"), py::arg("U_f"), py::arg("U_b"), py::arg("bh_f"),
-        py::arg("bh_b"), py::arg("y_f"), py::arg("y_b"), py::arg("hx_f"), py::arg("hx_b"), py::arg("hs_f"),
-        py::arg("hs_b"), py::arg("gates_f"), py::arg("gates_b"), py::arg("flags"), py::arg("err"), py::arg("T"),
-        py::arg("N"), py::arg("NP"), py::arg("H"), py::arg("BG"), py::arg("steps"), py::arg("gstride"),
-        py::arg("ndir"), py::arg("cell"), py::arg("nw"), py::arg("mt"), py::arg("persistent"), py::arg("timeout"),
-        py::arg("stamps") = py::none());
-  m.def("rnn_bwd", &rnn_bwd, py::arg("dy"), py::arg("lens"), py::arg("U_f"), py::arg("U_b"), py::arg("hs_f"),
-        py::arg("hs_b"), py::arg("gates_f"), py::arg("gates_b"), py::arg("dgh_f"), py::arg("dgh_b"), py::arg("dgx"),
-        py::arg("carry_f"), py::arg("carry_b"), py::arg("flags"), py::arg("err"), py::arg("T"), py::arg("N"),
-        py::arg("NP"), py::arg("H"), py::arg("BG"), py::arg("steps"), py::arg("gstride"), py::arg("ndir"),
-        py::arg("cell"), py::arg("nw"), py::arg("mt"), py::arg("persistent"), py::arg("timeout"),
-        py::arg("stamps") = py::none(), py::arg("dbx_part") = py::none(), py::arg("dbh_part") = py::none(),
-        py::arg("dgx_scale") = 1.0);
+  m.def("rnn_fwd", &rnn_fwd);
+  m.def("rnn_bwd", &rnn_bwd);
   m.def("rnn_kpw", &rnn_kpw);
   m.def("rnnf8_fwd", &rnnf8_fwd);
   m.def("rnnf8_supported", [](int64_t H, int64_t N, int64_t ndir) { return ds2_rnnf8_supported((int)H, (int)N, (int)ndir); });
@@ -1420,29 +1323,19 @@ PYBIND11_MODULE(_C, m) {
     return ds2_rnnf8_bwd_supported((int)H, (int)N, (int)ndir);
   });
   m.def("rnnf8_ring_words", [](int64_t H, int64_t BG, int64_t R) { return ds2_rnnf8_ring_words((int)H, (int)BG, (int)R); });
-  m.def("rnnx_fwd", &rnnx_fwd, py::arg("gx"), py::arg("lens"), py::arg("U_f"), py::arg("U_b"), py::arg("bh_f"),
-        py::arg("bh_b"), py::arg("y_f"), py::arg("y_b"), py::arg("hx_f"), py::arg("hx_b"), py::arg("hs_f"),
-        py::arg("hs_b"), py::arg("gates_f"), py::arg("gates_b"), py::arg("census"), py::arg("err"), py::arg("T"),
-        py::arg("N"), py::arg("NP"), py::arg("H"), py::arg("BG"), py::arg("R"), py::arg("steps"), py::arg("gstride"),
-        py::arg("ndir"), py::arg("cell"), py::arg("mt"), py::arg("timeout"), py::arg("xcd_map"), py::arg("knobs"),
-        py::arg("stamps") = py::none(), py::arg("ysum") = py::none());
-  m.def("rnnx_fwd_family", [](int64_t H, int64_t cell, int64_t mt, int64_t knobs) {
-    return ds2_rnnx_fwd_family((int)H, (int)cell, (int)mt, (int)knobs);
+  m.def("rnnx_fwd", &rnnx_fwd);
+  m.def("rnnx_bwd", &rnnx_bwd);
+  m.def("rnnx_members", [](int64_t H, int64_t cell) { return ds2_rnnx_members((int)H, (int)cell); });
+  m.def("rnnx_fwd_family", [](int64_t H, int64_t cell, int64_t knobs) {
+    return ds2_rnnx_fwd_family((int)H, (int)cell, (int)knobs);
   });
-  m.def("rnnx_bwd_family", [](int64_t H, int64_t cell, int64_t mt, int64_t R) {
-    return ds2_rnnx_bwd_family((int)H, (int)cell, (int)mt, (int)R);
+  m.def("rnnx_bwd_family", [](int64_t H, int64_t cell, int64_t R) { return ds2_rnnx_bwd_family((int)H, (int)cell, (int)R); });
+  m.def("rnnx_fwd_fuses_sum", [](int64_t H, int64_t cell, int64_t ndir, int64_t knobs) {
+    return ds2_rnnx_fwd_fuses_sum((int)H, (int)cell, (int)ndir, (int)knobs) != 0;
   });
-  m.def("rnnx_fwd_fuses_sum", [](int64_t H, int64_t cell, int64_t mt, int64_t ndir, int64_t knobs) {
-    return ds2_rnnx_fwd_fuses_sum((int)H, (int)cell, (int)mt, (int)ndir, (int)knobs) != 0;
+  m.def("rnnx_grid", [](int64_t H, int64_t cell, int64_t ngroups, int64_t xcd_map) {
+    return ds2_rnnx_grid((int)H, (int)cell, (int)ngroups, (int)xcd_map);
   });
-  m.def("rnnx_bwd", &rnnx_bwd, py::arg("dy"), py::arg("lens"), py::arg("U_f"), py::arg("U_b"), py::arg("hs_f"),
-        py::arg("hs_b"), py::arg("gates_f"), py::arg("gates_b"), py::arg("dgh_f"), py::arg("dgh_b"), py::arg("dgx"),
-        py::arg("dbx_part"), py::arg("dbh_part"), py::arg("dgx_scale"), py::arg("census"), py::arg("err"),
-        py::arg("T"), py::arg("N"), py::arg("NP"), py::arg("H"), py::arg("BG"), py::arg("R"), py::arg("steps"),
-        py::arg("gstride"), py::arg("ndir"), py::arg("cell"), py::arg("mt"), py::arg("timeout"), py::arg("xcd_map"),
-        py::arg("knobs"), py::arg("stamps") = py::none(), py::arg("ring_f") = py::none(),
-        py::arg("ring_b") = py::none());
-  m.def("rnnx_info", &rnnx_info);
   m.def("rnnx_ring_floats", [](int64_t H, int64_t BG, int64_t R) { return ds2_rnnx_ring_floats((int)H, (int)BG, (int)R); });
   m.def("ctc_fused", &ctc_fused);
   m.def("ctc_ws_floats", &ctc_ws_floats);
@@ -1537,3 +1430,4 @@ PYBIND11_MODULE(_C, m) {
     check(ds2_spin(ticks, (int)blocks, (int)threads, (int)lds_bytes, done.data_ptr<int>(), cur_stream()), "spin");
   });
 }
+

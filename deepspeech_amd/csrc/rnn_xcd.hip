@@ -2503,32 +2503,38 @@ static int gen2_kb(int H) {
   return need <= 6 ? need : -1;
 }
 
-static bool gen4_ok(int H, int cell, int mt, int knobs) {
+static bool gen4_ok(int H, int cell, int knobs) {
   const int kbq = (H / 32 + 3) / 4;
-  if ((knobs & 256) || mt != 1) return false;
+  if (knobs & 256) return false;
   if (cell == CELL_GRU) return kbq <= 7 || (kbq <= 10 && (H / 32) % 4 == 0 && !(knobs & 65536));
   return kbq <= 8;
 }
 
 // Which forward kernel family ds2_rnnx_fwd launches for a geometry (the dispatch below and
 // the report binding rnnx_fwd_family share this one function): 6 rnnw (wide one-gate), 5 rnne
-// (GRU, K-eighths), 4 rnnq (K-quarters), 2 rnnx (generation 2); 0 = not covered (-30/-31/-33)
-int ds2_rnnx_fwd_family(int H, int cell, int mt, int knobs) {
+// (GRU, K-eighths), 4 rnnq (K-quarters), 2 rnnx (generation 2); 0 = not covered (-30/-31)
+int ds2_rnnx_fwd_family(int H, int cell, int knobs) {
   if (wide_ok(H, cell)) return 6;
-  if (H % UPW != 0 || mt != 1 || gen2_kb(H) < 0) return 0;
-  if (gen4_ok(H, cell, mt, knobs)) return (cell == CELL_GRU && H / 32 <= 32) ? 5 : 4;
+  if (H % UPW != 0 || gen2_kb(H) < 0) return 0;
+  if (gen4_ok(H, cell, knobs)) return (cell == CELL_GRU && H / 32 <= 32) ? 5 : 4;
   return 2;
 }
 
 // BPTT family of ds2_rnnx_bwd_rs: 6 rnnw_bwd, 3 rnnrs (reduce-scatter), 0 = not covered
-int ds2_rnnx_bwd_family(int H, int cell, int mt, int R) {
-  if (wide_ok(H, cell)) return (R >= 1 && R <= 8 && mt == 1 && xcd_p(H, cell) <= 4 * MW) ? 6 : 0;
-  if (H % UPW != 0 || R < 1 || R > 16 || mt != 1 || H / UPW > 6 * MW) return 0;
+int ds2_rnnx_bwd_family(int H, int cell, int R) {
+  if (wide_ok(H, cell)) return (R >= 1 && R <= 8 && xcd_p(H, cell) <= 4 * MW) ? 6 : 0;
+  if (H % UPW != 0 || R < 1 || R > 16 || H / UPW > 6 * MW) return 0;
   return (H / 16 + MW - 1) / MW <= 12 ? 3 : 0;          // rnnrs_bwd_kernel's unit tiles (-36 past)
 }
 
-int ds2_rnnx_fwd_fuses_sum(int H, int cell, int mt, int ndir, int knobs) {
-  return ndir == 2 && mt == 1 && (wide_ok(H, cell) || gen4_ok(H, cell, mt, knobs)) ? 1 : 0;
+// Workgroups per group for a layer width, 0 where this file has no forward and BPTT for it
+// (ops/rnn.py make_xcd_plan builds its plans from this and the two family functions)
+int ds2_rnnx_members(int H, int cell) {
+  return ds2_rnnx_fwd_family(H, cell, 0) && ds2_rnnx_bwd_family(H, cell, 1) ? xcd_p(H, cell) : 0;
+}
+
+int ds2_rnnx_fwd_fuses_sum(int H, int cell, int ndir, int knobs) {
+  return ndir == 2 && (wide_ok(H, cell) || gen4_ok(H, cell, knobs)) ? 1 : 0;
 }
 
 // grid size of a launch (blocks with no role exit at once)
@@ -2538,7 +2544,7 @@ int ds2_rnnx_grid(int H, int cell, int ngroups, int xcd_map) {
 }
 
 static int rnnw_fwd(const DS2RnnX* d, hipStream_t st) {
-  if (d->R < 1 || d->R > 8 || d->mt != 1 || d->NP != d->BG * d->R) return -30;
+  if (d->R < 1 || d->R > 8 || d->NP != d->BG * d->R) return -30;
   const XFwd a = make_xfwd(d, xcd_p(d->H, d->cell));
   if (d->ysum != nullptr && d->ndir != 2) return -37;
   if (d->steps <= 0) return 0;
@@ -2559,7 +2565,7 @@ static int rnnw_fwd(const DS2RnnX* d, hipStream_t st) {
 
 int ds2_rnnx_fwd(const DS2RnnX* d, hipStream_t st) {
   if (wide_ok(d->H, d->cell)) return rnnw_fwd(d, st);
-  if (d->H % UPW != 0 || d->R < 1 || d->R > 16 * d->mt || d->NP != d->BG * d->R) return -30;
+  if (d->H % UPW != 0 || d->R < 1 || d->R > 16 || d->NP != d->BG * d->R) return -30;
   const int kb = gen2_kb(d->H);
   if (kb < 0) return -31;
   const XFwd a = make_xfwd(d, d->H / UPW);
@@ -2569,7 +2575,7 @@ int ds2_rnnx_fwd(const DS2RnnX* d, hipStream_t st) {
   const int kbq = (d->H / 32 + 3) / 4;
   // (GRU at kbq = 8 spills under the 3-waves-per-SIMD register budget: kbq 8..10 keep
   // kbq - 7 k-steps of U in LDS)
-  const int fam = ds2_rnnx_fwd_family(d->H, d->cell, d->mt, d->knobs);
+  const int fam = ds2_rnnx_fwd_family(d->H, d->cell, d->knobs);
   const bool gen4 = fam == 4 || fam == 5;
   if (d->ysum != nullptr && (!gen4 || d->ndir != 2)) return -37;   // only gen 4 / 5 fuse the sum
   // generation 5 (K-eighths, each granule polled once) for GRU layers with H <= 1024
@@ -2614,7 +2620,6 @@ int ds2_rnnx_fwd(const DS2RnnX* d, hipStream_t st) {
     return (int)hipGetLastError();
   }
   // generation 2: no dynamic LDS (the exchanged state goes straight into MFMA registers)
-  if (d->mt != 1) return -33;     // 16-row tiles only: the 32-row LDS footprint exceeds 160 KB
   return d->cell == CELL_GRU ? launch_fwd<CELL_GRU, 1>(a, kb, grid, st) : launch_fwd<CELL_RELU, 1>(a, kb, grid, st);
 }
 
@@ -2622,7 +2627,7 @@ int ds2_rnnx_fwd(const DS2RnnX* d, hipStream_t st) {
 long long ds2_rnnx_ring_floats(int H, int BG, int R) { return 3LL * BG * (H / UPW) * R * H; }
 
 static int rnnw_bwd(const DS2RnnX* d, hipStream_t st) {
-  if (d->R < 1 || d->R > 8 || d->mt != 1 || d->NP != d->BG * d->R) return -30;
+  if (d->R < 1 || d->R > 8 || d->NP != d->BG * d->R) return -30;
   if (d->ring[0] == nullptr || (d->ndir == 2 && d->ring[1] == nullptr)) return -34;
   const int P = xcd_p(d->H, d->cell);
   if (P > 4 * MW) return -35;                         // GPT = 4 producers per gather thread
@@ -2646,7 +2651,7 @@ static int rnnw_bwd(const DS2RnnX* d, hipStream_t st) {
 
 int ds2_rnnx_bwd_rs(const DS2RnnX* d, hipStream_t st) {
   if (wide_ok(d->H, d->cell)) return rnnw_bwd(d, st);
-  if (d->H % UPW != 0 || d->R < 1 || d->R > 16 || d->NP != d->BG * d->R || d->mt != 1) return -30;
+  if (d->H % UPW != 0 || d->R < 1 || d->R > 16 || d->NP != d->BG * d->R) return -30;
   if (d->ring[0] == nullptr || (d->ndir == 2 && d->ring[1] == nullptr)) return -34;
   const int P = d->H / UPW;
   if (P > 6 * MW) return -35;                       // at most GPT = 6 producers per gather thread

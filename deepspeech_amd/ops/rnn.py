@@ -137,48 +137,6 @@ _FUSE_DIRSUM = True        # module switch: tests compare the fused direction su
 _DU_SPLITS = 2
 
 
-LDS_BYTES = 160 * 1024
-
-
-def _xcd_kb(H: int) -> int:
-    """k-steps per MFMA wave of the generation-2 forward of csrc/rnn_xcd.hip (K split over the
-    7 worker waves; the 8th is the memory wave). -1 if the tile would not fit."""
-    need = -(-(H // 32) // 7)
-    return need if need <= 6 else -1
-
-
-def _rs_ok(H: int) -> bool:
-    """The reduce-scatter BPTT (generation 3) serves P = H/32 <= 42 workgroups per group.
-    Groups wider than one XCD (P > 32) exchange write-through across XCDs; measured on
-    MI355X that still beats the generation-1 kernels for the 3-gate GRU (H=1280: fwd 1.52 vs
-    1.93, BPTT 2.05 vs 3.68 ms per layer) but not for the one-gate clipped ReLU (H=1760 with
-    8-producer gathers: 1.84 / 2.35 vs 1.26 / 1.41): those layers run the 64-unit wide
-    kernels instead (_wide_ok)."""
-    return H // 32 <= 42
-
-
-def _xcd_lds(H: int, G: int, mt: int) -> int:
-    """Static LDS bytes of the larger of the two csrc/rnn_xcd.hip kernels (16-row tiles only)."""
-    if mt != 1 or _xcd_kb(H) < 0 or not _rs_ok(H):
-        return 1 << 30
-    # forward + reduce-scatter BPTT (static, ~61 KB at G = 3)
-    return 2 * 7 * 16 * (G * 32 + 1) * 4 + 16 * 32 * 2 + 2 * 16 * G * 32 * 4 + 2 * 2 * 16 * 32 * 4 \
-        + (2 * 16 * 32 * 16 if G == 3 else 16) + 16 * 4 + G * 32 * 4 + 64
-
-
-def _wide_ok(H: int, cell: str) -> bool:
-    """One-gate layers wider than an XCD at 32 units per workgroup (32 < H/32, H <= 1792, e.g.
-    the reference's ReLU-1760) run the 64-unit wide kernels of csrc/rnn_xcd.hip (rnnw_*):
-    P = ceil(H/64) <= 28 workgroups per group, one XCD. (Two 32-unit workgroups per CU also
-    kept such a group on one XCD but measured slower: profiles/r3_negative_results.md.)"""
-    return cell == "rnn_relu" and H % 32 == 0 and H // 32 > 32 and H <= 1792
-
-
-def _xcd_p(H: int, cell: str) -> int:
-    """Workgroups per group of an XCD-kernel plan."""
-    return -(-H // 64) if _wide_ok(H, cell) else H // 32
-
-
 # geometry experiments (tools/bench_rnn.py): minimum rows per XCD group (0: the plan's choice),
 # generation-1 waves per workgroup (0: the plan's choice)
 _MIN_ROWS = 0
@@ -186,44 +144,44 @@ _FORCE_NW = 0
 
 
 def make_xcd_plan(N: int, H: int, cell: str, ndir: int, cus: int) -> Optional[RnnPlan]:
-    """Generation-2 geometry: groups of R batch rows x all H units (H/32 workgroups of 32
-    units). Prefer the most groups that still fit the chip (smaller per-step gathers), at
-    most 8 so a group can live on one XCD; rows per group R <= 32."""
-    G = GATES[cell]
-    P = H // 32
-    if _wide_ok(H, cell):
-        # 8 groups (one per XCD) of R <= 8 rows: the wide BPTT's two-producers-per-load gather
-        Pw = _xcd_p(H, cell)
+    """Geometry for csrc/rnn_xcd.hip: groups of R batch rows x all H units, P workgroups each.
+    What the kernels cover is the extension's to say (rnnx_members: P, 0 if the width is not
+    served; rnnx_fwd_family / rnnx_bwd_family: the kernels a geometry launches, 0 for none);
+    what is chosen among the covered geometries was measured and is decided here. Prefer the
+    most groups that still fit the chip (smaller per-step gathers), at most 8 so a group can
+    live on one XCD."""
+    C = _ext.ext()
+    code = CELL_CODE[cell]
+    P = int(C.rnnx_members(H, code))
+    if P == 0:
+        return None
+    if int(C.rnnx_fwd_family(H, code, 0)) == 6:
+        # the wide one-gate kernels, 64 units per workgroup: 8 groups (one per XCD) of R <= 8 rows,
+        # the wide BPTT's two-producers-per-load gather. (At 32 units per workgroup ReLU-1760
+        # spanned XCDs and lost to generation 1, 1.84 / 2.35 vs 1.26 / 1.41 ms per layer; two
+        # 32-unit workgroups per CU measured slower too: profiles/r3_negative_results.md.)
         BG = 8 // ndir
         R = -(-N // BG)
-        if R > 8 or ndir * BG * Pw > cus or Pw > cus // 8:
+        if R > 8 or ndir * BG * P > cus or P > cus // 8:
             return None
-        return RnnPlan(N=N, NP=BG * R, BG=BG, mt=1, nw=8, persistent=True, H=H, S=H // 16, cell=cell,
-                       ndir=ndir, kind="xcd", R=R, xcd_map=1)
-    wide = 42 if (_rs_ok(H) and G == 3) else 32         # see _rs_ok
-    if H % 32 != 0 or P > wide:          # larger H: the resident U slice would spill
-        return None
-    best = None
-    # groups wider than an XCD (P > CUs/8) exchange across XCDs (write-through): fewer,
-    # taller groups measured faster there (H=1280: R=16 27.9 vs R=11 30.3 ms/step)
-    minr = _MIN_ROWS or (min(16, N) if P > cus // 8 else 1)
-    for R in range(max(1, minr), 33):
+        xcd_map = 1
+    else:
+        # groups wider than an XCD (P > CUs/8) exchange across XCDs (write-through): fewer,
+        # taller groups measured faster there (H=1280: R=16 27.9 vs R=11 30.3 ms/step). That
+        # still beats generation 1 for the 3-gate GRU (H=1280: fwd 1.52 vs 1.93, BPTT 2.05 vs
+        # 3.68 ms per layer); one-gate layers of that width run the wide kernels above.
+        def fits(R):
+            ngroups = ndir * -(-N // R)
+            # more than 8 small groups: no XCD locality, keep MFMA rows full
+            return ngroups * P <= cus and (ngroups <= 8 or R >= 16)
+        R = max(1, _MIN_ROWS or (min(16, N) if P > cus // 8 else 1))
+        while C.rnnx_bwd_family(H, code, R) and not fits(R):
+            R += 1
         BG = -(-N // R)
-        ngroups = ndir * BG
-        if ngroups * P > cus:
-            continue
-        if ngroups > 8 and R < 16:
-            continue                       # many small groups: no XCD locality, keep MFMA rows full
-        mt = 1 if R <= 16 else 2
-        if _xcd_lds(H, G, mt) > LDS_BYTES:
-            continue
-        best = (R, BG, mt)
-        break
-    if best is None:
+        xcd_map = int(ndir * BG <= 8 and P <= cus // 8)
+    if not C.rnnx_bwd_family(H, code, R):
         return None
-    R, BG, mt = best
-    xcd_map = int(ndir * BG <= 8 and P <= cus // 8)
-    return RnnPlan(N=N, NP=BG * R, BG=BG, mt=mt, nw=8, persistent=True, H=H, S=H // 16, cell=cell,
+    return RnnPlan(N=N, NP=BG * R, BG=BG, mt=1, nw=8, persistent=True, H=H, S=H // 16, cell=cell,
                    ndir=ndir, kind="xcd", R=R, xcd_map=xcd_map)
 
 
@@ -240,12 +198,8 @@ _MAX_KPW = {
 
 
 def _kpw(H: int, G: int, nw: int, fwd: bool) -> int:
-    ks = (H // 32) if fwd else (G * H // 32)
-    need = -(-ks // nw)
-    for k in (4, 8, 12, 16, 24, 32):
-        if k >= need:
-            return k
-    return -1
+    """k-steps per wave of the generation-1 instantiation (csrc/rnn_persistent.hip), -1 for none"""
+    return int(_ext.ext().rnn_kpw(H, G, nw, fwd))
 
 
 def _fits(cell: str, H: int, nw: int, mt: int) -> bool:
@@ -334,7 +288,7 @@ def _gate(census: Optional[torch.Tensor], plan: Optional["RnnPlan"]) -> None:
         # a replayed graph orders its nodes itself (one queue, DEBUG_HIP_FORCE_GRAPH_QUEUES):
         # a spin on a launch the replay may issue after it would only wait for its timeout
         return
-    last = plan.ndir * plan.BG * _xcd_p(plan.H, plan.cell) - 1
+    last = _bptt_cus(plan) - 1
     if 0 <= last < census.numel():
         _ext.ext().wait_resident(census[last:last + 1], _GATE_TICKS)
 
@@ -345,9 +299,13 @@ def _next_bptt(dev: torch.device):
     return (pre[2][0], pre[0]) if pre is not None else (None, None)
 
 
-def _stamps(kind: str, plan: "RnnPlan", grid: int, dev) -> Optional[torch.Tensor]:
+def _stamps(kind: str, plan: "RnnPlan", dev) -> Optional[torch.Tensor]:
+    """The [workgroups, 8] stamp buffer of a launch while STAMP_LOG records, else None."""
     if STAMP_LOG is None:
         return None
+    grid = plan.ndir * plan.BG * plan.S
+    if plan.kind == "xcd":      # blocks with no role exit at once
+        grid = int(_ext.ext().rnnx_grid(plan.H, CELL_CODE[plan.cell], plan.ndir * plan.BG, plan.xcd_map))
     t = torch.zeros(grid, 8, device=dev, dtype=torch.int64)
     STAMP_LOG.append((kind, plan, t))
     return t
@@ -470,7 +428,7 @@ def _alloc_fwd(T: int, N: int, plan: RnnPlan, dev) -> _FwdBufs:
     # sum buffer, one direction writes through, the other adds): no torch.add launch and no
     # per-direction output round trip
     b.fuse = (plan.kind == "xcd" and d1 and _FUSE_DIRSUM and
-              bool(C.rnnx_fwd_fuses_sum(H, CELL_CODE[plan.cell], plan.mt, ndir, _kernel_knobs(plan))))
+              bool(C.rnnx_fwd_fuses_sum(H, CELL_CODE[plan.cell], ndir, _kernel_knobs(plan))))
     b.y2 = None if b.fuse else torch.empty(ndir, T, N, H, device=dev, dtype=bf16)
     b.ysum = torch.empty(T, N, H, device=dev, dtype=bf16) if b.fuse else None
     b.hx = torch.empty(ndir, T + 1, plan.NP, H, device=dev, dtype=bf16)
@@ -495,6 +453,14 @@ def _fill_fwd(b: _FwdBufs, plan: RnnPlan) -> None:
     _ext.ext().multi_fill(*_fill_regions(b, plan))
 
 
+def _geom(plan: RnnPlan, T: int, N: int, gstride: int, tiling: Optional[tuple] = None) -> tuple:
+    """The geometry integers every recurrence binding takes, in the field order of DS2RnnGeom
+    (csrc/api.h), for a launch over all T steps. tiling: (NP, BG, R, xcd_map) where they are not
+    the plan's (the fp8 kernels' own row tiling)."""
+    NP, BG, R, xcd_map = tiling or (plan.NP, plan.BG, plan.R, plan.xcd_map)
+    return (T, N, NP, plan.H, BG, R, T, gstride, plan.ndir, xcd_map, CELL_CODE[plan.cell], _kernel_knobs(plan))
+
+
 def _run_fwd(gx, lens, U, bh, plan: RnnPlan, h0=None, bufs: Optional[_FwdBufs] = None):
     """Launch the persistent forward recurrence over gx [T, N, ndir*G*H] (bf16).
     U / bh: per-direction lists (bf16 [G*H, H] / fp32 [G*H] or None).
@@ -504,30 +470,20 @@ def _run_fwd(gx, lens, U, bh, plan: RnnPlan, h0=None, bufs: Optional[_FwdBufs] =
     Returns (y [T, N, H] bf16 = sum of directions, saved-state tuple)."""
     C = _ext.ext()
     T, N, gstride = gx.shape
-    H, ndir = plan.H, plan.ndir
-    steps = T
+    ndir = plan.ndir
     dev = gx.device
     d1 = ndir == 2
     b = bufs if bufs is not None else _alloc_fwd(T, N, plan, dev)
     fuse, y2, ysum, hx, hs, gates = b.fuse, b.y2, b.ysum, b.hx, b.hs, b.gates
+    geom = _geom(plan, T, N, gstride)
     if plan.kind == "xcd":
-        census = b.census
-        err = error_word(dev)
         if bufs is None:
             _fill_fwd(b, plan)
         if h0 is not None:
             hs[:, 0, :N].copy_(h0)
             hx[:, 0, :N].copy_(h0)
-        yf, yb = (ysum, ysum) if fuse else (y2[0], y2[1] if d1 else None)
-        C.rnnx_fwd(gx, lens, U[0], U[1] if d1 else None, bh[0], bh[1] if d1 else None,
-                   yf, yb, hx[0], hx[1] if d1 else None,
-                   hs[0], hs[1] if d1 else None,
-                   gates[0] if gates is not None else None,
-                   gates[1] if (gates is not None and d1) else None,
-                   census, err, T, N, plan.NP, H, plan.BG, plan.R, steps, gstride, ndir,
-                   CELL_CODE[plan.cell], plan.mt, TIMEOUT_TICKS, plan.xcd_map, _kernel_knobs(plan),
-                   _stamps("fwd", plan, int(C.rnnx_info(H, GATES[plan.cell], ndir * plan.BG,
-                                                         plan.xcd_map)["grid"]), dev), ysum)
+        C.rnnx_fwd(geom, gx, lens, U[0], U[1] if d1 else None, bh[0], bh[1] if d1 else None, y2, ysum, hx, hs,
+                   gates, b.census, error_word(dev), TIMEOUT_TICKS, _stamps("fwd", plan, dev))
         y = ysum if fuse else (torch.add(y2[0], y2[1]) if d1 else y2[0])
         return y, (hx, hs, gates if gates is not None else torch.empty(0, device=dev))
     hx[:, 0].zero_()                         # h0
@@ -535,17 +491,9 @@ def _run_fwd(gx, lens, U, bh, plan: RnnPlan, h0=None, bufs: Optional[_FwdBufs] =
     if h0 is not None:
         hs[:, 0, :N].copy_(h0)
         hx[:, 0, :N].copy_(h0)
-    err = error_word(dev)
     flags = torch.zeros(ndir * plan.BG * plan.S, device=dev, dtype=torch.int32)
-    C.rnn_fwd(gx, lens, U[0], U[1] if d1 else None,
-              bh[0], bh[1] if d1 else None,
-              y2[0], y2[1] if d1 else None, hx[0], hx[1] if d1 else None,
-              hs[0], hs[1] if d1 else None,
-              gates[0] if gates is not None else None,
-              gates[1] if (gates is not None and d1) else None,
-              flags, err, T, N, plan.NP, H, plan.BG, steps, gstride, ndir,
-              CELL_CODE[plan.cell], plan.nw, plan.mt, plan.persistent, TIMEOUT_TICKS,
-              _stamps("fwd", plan, flags.numel(), dev))
+    C.rnn_fwd(geom, plan.nw, plan.mt, plan.persistent, gx, lens, U[0], U[1] if d1 else None,
+              bh[0], bh[1] if d1 else None, y2, hx, hs, gates, flags, error_word(dev), TIMEOUT_TICKS, _stamps("fwd", plan, dev))
     y = torch.add(y2[0], y2[1]) if d1 else y2[0]
     return y, (hx, hs, gates if gates is not None else torch.empty(0, device=dev))
 
@@ -564,8 +512,8 @@ def kernel_families(plan: RnnPlan) -> Tuple[str, str]:
         g1 = "rnn_%s (gen 1, " + ("persistent)" if plan.persistent else "step launches)")
         return g1 % "fwd", g1 % "bwd"
     C = _ext.ext()
-    f = int(C.rnnx_fwd_family(plan.H, CELL_CODE[plan.cell], plan.mt, _kernel_knobs(plan)))
-    b = int(C.rnnx_bwd_family(plan.H, CELL_CODE[plan.cell], plan.mt, plan.R))
+    f = int(C.rnnx_fwd_family(plan.H, CELL_CODE[plan.cell], _kernel_knobs(plan)))
+    b = int(C.rnnx_bwd_family(plan.H, CELL_CODE[plan.cell], plan.R))
     if f not in _FWD_FAMILY or b not in _BWD_FAMILY:
         raise ValueError("xcd plan not covered by csrc/rnn_xcd.hip: %r" % (plan,))
     return _FWD_FAMILY[f], _BWD_FAMILY[b]
@@ -624,8 +572,8 @@ def _run_fwd_fp8(gx, lens, U, bh, plan: RnnPlan, keep: Optional[dict] = None, pa
     C.multi_fill([hq[d, 0] for d in range(ndir)] + [hq[d, 1:] for d in range(ndir)] + [census],
                  [0] * ndir + [-1] * ndir + [-1])
     C.multi_fill([hx[d, 0] for d in range(ndir)] + [hs[d, 0] for d in range(ndir)], [0] * (2 * ndir))
-    C.rnnf8_fwd(gx.contiguous(), lens, U8, words, bh[0], bh[1] if ndir == 2 else None, y2, hq, hx, hs, gates, census,
-                error_word(dev), T, N, NP, H, BG, R, T, gstride, ndir, TIMEOUT_TICKS, 1)
+    C.rnnf8_fwd(_geom(plan, T, N, gstride, (NP, BG, R, 1)), gx.contiguous(), lens, U8, words,
+                bh[0], bh[1] if ndir == 2 else None, y2, hq, hx, hs, gates, census, error_word(dev), TIMEOUT_TICKS)
     y = (y2 if pair else torch.add(y2[0], y2[1])) if ndir == 2 else y2[0]
     return y, (hx, hs, gates)
 
@@ -666,9 +614,8 @@ def _run_bwd_fp8(dy, lens, U, hs, gates, plan: RnnPlan, gstride: int, dgx_scale:
     parts = torch.empty(2, ndir, BG, 3 * H, device=dev, dtype=torch.float32) if want_bias else None
     ring = torch.empty(ndir, int(C.rnnf8_ring_words(H, BG, R)), device=dev, dtype=torch.int32)
     _fill_bwd(census, parts, ring)
-    C.rnnf8_bwd(dy, lens, U8T, words, hs, gates, dgh, dgx, parts[0] if parts is not None else None,
-                parts[1] if parts is not None else None, float(dgx_scale), census, error_word(dev), ring,
-                T, N, NP, H, BG, R, steps, gstride, ndir, TIMEOUT_TICKS, 1)
+    C.rnnf8_bwd(_geom(plan, T, N, gstride, (NP, BG, R, 1)), dy, lens, U8T, words, hs, gates, dgh, dgx, parts,
+                float(dgx_scale), census, error_word(dev), ring, TIMEOUT_TICKS)
     return dgx, dgh, parts
 
 
@@ -723,9 +670,9 @@ def _run_bwd(dy, lens, U, hx, hs, gates, plan: RnnPlan, gstride: int, dgx_scale:
     dy = dy.to(torch.bfloat16).contiguous()
     dgh = torch.empty(ndir, steps, plan.NP, G * H, device=dev, dtype=torch.bfloat16)
     dgx = torch.empty(T, N, gstride, device=dev, dtype=torch.bfloat16)
-    has_g = gates.numel() > 0
+    gates = gates if gates.numel() > 0 else None
+    geom = _geom(plan, T, N, gstride)
     if plan.kind == "xcd":
-        err = error_word(dev)
         # generation-3 BPTT: reduce-scatter of partials through a 3-slot ring (readiness =
         # per-use tag in each word's LSB, ring filled with 0xFFFFFFFF); dgh is a plain output
         pre = _BWD_PREFILL.pop(dev.index, None)
@@ -735,32 +682,15 @@ def _run_bwd(dy, lens, U, hx, hs, gates, plan: RnnPlan, gstride: int, dgx_scale:
         else:
             census, parts, ring = _alloc_bwd(plan, want_bias, dev)
             _fill_bwd(census, parts, ring)
-        C.rnnx_bwd(dy, lens, U[0], U[1] if d1 else None, hs[0], hs[1] if d1 else None,
-                   gates[0] if has_g else None, gates[1] if (has_g and d1) else None,
-                   dgh[0], dgh[1] if d1 else None, dgx,
-                   parts[0] if parts is not None else None,
-                   parts[1] if (parts is not None and plan.cell == "gru") else None,
-                   float(dgx_scale), census, err, T, N, plan.NP, H, plan.BG, plan.R, steps, gstride, ndir,
-                   CELL_CODE[plan.cell], plan.mt, TIMEOUT_TICKS, plan.xcd_map, _kernel_knobs(plan),
-                   _stamps("bwd", plan, int(C.rnnx_info(H, G, ndir * plan.BG, plan.xcd_map)["grid"]), dev),
-                   ring[0], ring[1] if d1 else None)
+        C.rnnx_bwd(geom, dy, lens, U[0], U[1] if d1 else None, hs, gates, dgh, dgx, parts, float(dgx_scale), census,
+                   error_word(dev), ring, TIMEOUT_TICKS, _stamps("bwd", plan, dev))
         return dgx, dgh, parts
-    err = error_word(dev)
     parts = torch.zeros(2 if plan.cell == "gru" else 1, ndir, plan.BG, G * H, device=dev,
                         dtype=torch.float32) if want_bias else None
     carry = None if plan.persistent else torch.zeros(ndir, plan.NP, H, device=dev, dtype=torch.float32)
     flags = torch.zeros(ndir * plan.BG * plan.S, device=dev, dtype=torch.int32)
-    C.rnn_bwd(dy, lens, U[0], U[1] if d1 else None, hs[0], hs[1] if d1 else None,
-              gates[0] if has_g else None, gates[1] if (has_g and d1) else None,
-              dgh[0], dgh[1] if d1 else None, dgx,
-              carry[0] if carry is not None else None,
-              carry[1] if (carry is not None and d1) else None,
-              flags, err, T, N, plan.NP, H, plan.BG, steps, gstride, ndir,
-              CELL_CODE[plan.cell], plan.nw, plan.mt, plan.persistent, TIMEOUT_TICKS,
-              _stamps("bwd", plan, flags.numel(), dev),
-              parts[0] if parts is not None else None,
-              parts[1] if (parts is not None and plan.cell == "gru") else None,
-              float(dgx_scale))
+    C.rnn_bwd(geom, plan.nw, plan.mt, plan.persistent, dy, lens, U[0], U[1] if d1 else None, hs, gates, dgh, dgx,
+              carry, parts, float(dgx_scale), flags, error_word(dev), TIMEOUT_TICKS, _stamps("bwd", plan, dev))
     return dgx, dgh, parts
 
 
@@ -1222,7 +1152,7 @@ _GROUP_BEFORE_DX = True
 def _bptt_cus(plan: RnnPlan) -> int:
     """CUs the persistent BPTT of ``plan`` occupies (one workgroup per CU)."""
     if plan.kind == "xcd":
-        return plan.ndir * plan.BG * _xcd_p(plan.H, plan.cell)
+        return plan.ndir * plan.BG * int(_ext.ext().rnnx_members(plan.H, CELL_CODE[plan.cell]))
     return plan.ndir * plan.BG * plan.S if plan.persistent else 1 << 30
 
 

@@ -113,7 +113,7 @@ def test_wide_relu_kernels(cuda, N, H, ndir):
     # (rnnw_fwd_kernel / rnnw_bwd_kernel): full and half-empty last workgroups (H % 64 == 32),
     # every LDS/register split of the U slice in use, one direction
     from deepspeech_amd.ops import rnn as RNN
-    assert RNN._wide_ok(H, "rnn_relu")
+    assert RNN._ext.ext().rnnx_fwd_family(H, RNN.CELL_CODE["rnn_relu"], 0) == 6
     p = RNN.make_xcd_plan(N, H, "rnn_relu", ndir, 256)
     assert p is not None and p.kind == "xcd" and p.xcd_map == 1 and p.R <= 8
     _rnn_case(cuda, "rnn_relu", N=N, H=H, T=37, ndir=ndir, mode="auto", seed=31)
@@ -126,6 +126,79 @@ def test_unirnn_gru(cuda):
 def test_birnn_mt2(cuda):
     # batch 96 with H=1280 forces two 16-row tiles per workgroup
     _rnn_case(cuda, "gru", N=96, H=1280, T=12, ndir=2, mode="auto", seed=7)
+
+
+class _Recorder:
+    """Stands in for the extension: passes everything through except the launch binding
+    ``name``, whose positional arguments it keeps instead of launching."""
+
+    def __init__(self, C, name):
+        self._C, self._name, self.args = C, name, None
+
+    def __getattr__(self, attr):
+        if attr != self._name:
+            return getattr(self._C, attr)
+        return lambda *args: setattr(self, "args", list(args))
+
+
+# positions of the stacked [ndir, ...] buffers in each recurrence launch binding (csrc/bindings.cpp)
+_STACKED = {
+    "rnn_fwd": {"y": 10, "hx": 11, "hs": 12, "gates": 13},
+    "rnn_bwd": {"hs": 8, "gates": 9, "dgh": 10, "carry": 12, "bias partials": 13},
+    "rnnx_fwd": {"y": 7, "hx": 9, "hs": 10, "gates": 11},
+    "rnnx_bwd": {"hs": 5, "gates": 6, "dgh": 7, "bias partials": 9, "ring": 13},
+    "rnnf8_fwd": {"y": 7, "hq": 8, "hx": 9, "hs": 10, "gates": 11},
+    "rnnf8_bwd": {"hs": 5, "gates": 6, "dgh": 7, "bias partials": 9, "ring": 13},
+}
+
+
+@pytest.mark.parametrize("family", ["v1", "xcd", "fp8"])
+def test_recurrence_bindings_refuse_wrong_buffers(cuda, monkeypatch, family):
+    """Every recurrence launch binding refuses a stacked buffer that is one element short, and
+    one of the wrong dtype, naming it, before anything is launched: the arguments ops/rnn.py
+    builds are recorded instead of launched, each buffer in turn is replaced (by a view of the
+    full allocation, or a larger one: nothing here could be overrun), and the untouched
+    arguments then launch cleanly -- the forward's really saved state feeds the BPTT's."""
+    import re
+    from deepspeech_amd.ops import rnn as RNN
+    torch.manual_seed(11)
+    N, H, T = (8, 256, 4) if family == "fp8" else (5, 64, 4)
+    plan = RNN.make_plan(N, H, "gru", 2, 256, "step" if family == "v1" else "auto")
+    assert plan.kind == ("v1" if family == "v1" else "xcd")
+    monkeypatch.setattr(RNN, "_FUSE_DIRSUM", False)        # y as the stacked direction pair
+    lens = torch.tensor([T] + [T - 1] * (N - 1), dtype=torch.int32, device=cuda)
+    gx = (torch.randn(T, N, 6 * H) * 0.5).bfloat16().to(cuda)
+    dy = torch.randn(T, N, H).bfloat16().to(cuda)
+    U = [(torch.randn(3 * H, H) / math.sqrt(H)).bfloat16().to(cuda) for _ in range(2)]
+    bh = [(torch.randn(3 * H) * 0.1).to(cuda) for _ in range(2)]
+    C = RNN._ext.ext()
+    fwd, bwd = {"v1": ("rnn_fwd", "rnn_bwd"), "xcd": ("rnnx_fwd", "rnnx_bwd"), "fp8": ("rnnf8_fwd", "rnnf8_bwd")}[family]
+
+    def refuses_then_launches(name, run):
+        rec = _Recorder(C, name)
+        monkeypatch.setattr(RNN._ext, "ext", lambda: rec)
+        out = run()
+        monkeypatch.setattr(RNN._ext, "ext", lambda: C)
+        assert rec.args is not None, name
+        for i, (buf, pos) in enumerate(_STACKED[name].items()):
+            good = rec.args[pos]
+            wrong = [good.flatten()[:-1]]
+            if i == 0:
+                wrong.append(torch.empty(good.numel(), device=cuda, dtype=torch.float64))
+            for w in wrong:
+                with pytest.raises(RuntimeError, match=re.escape(buf + " must be")):
+                    getattr(C, name)(*rec.args[:pos], w, *rec.args[pos + 1:])
+        getattr(C, name)(*rec.args)
+        return out
+
+    if family == "fp8":
+        _, (hx, hs, gates) = refuses_then_launches(fwd, lambda: RNN._run_fwd_fp8(gx, lens, U, bh, plan))
+        refuses_then_launches(bwd, lambda: RNN._run_bwd_fp8(dy, lens, U, hs, gates, plan, 6 * H))
+    else:
+        _, (hx, hs, gates) = refuses_then_launches(fwd, lambda: RNN._run_fwd(gx, lens, U, bh, plan))
+        refuses_then_launches(bwd, lambda: RNN._run_bwd(dy, lens, U, hx, hs, gates, plan, 6 * H))
+    torch.cuda.synchronize()
+    RNN.check_errors()
 
 
 # --------------------------------------------------------------------------- CTC
@@ -404,7 +477,7 @@ def test_fused_direction_sum_bitwise(cuda, cell):
     plan = RNN.plan_for(N, H, cell, 2, cuda)
     assert plan.kind == "xcd"
     C = _ext_mod().ext()
-    assert C.rnnx_fwd_fuses_sum(H, RNN.CELL_CODE[cell], plan.mt, 2, RNN.RNNX_KNOBS)
+    assert C.rnnx_fwd_fuses_sum(H, RNN.CELL_CODE[cell], 2, RNN.RNNX_KNOBS)
     old = RNN._FUSE_DIRSUM
     try:
         ys = []

@@ -159,10 +159,11 @@ def test_xcd_plans_for_wide_and_deferral_rule():
     from deepspeech_amd.ops import rnn as RNN
     p = RNN.make_xcd_plan(32, 1760, "rnn_relu", 2, 256)
     assert p is not None and p.kind == "xcd" and (p.BG, p.R, p.NP, p.xcd_map) == (4, 8, 32, 1)
-    assert RNN._xcd_p(1760, "rnn_relu") == 28 and RNN._bptt_cus(p) == 224
+    C, relu, gru = RNN._ext.ext(), RNN.CELL_CODE["rnn_relu"], RNN.CELL_CODE["gru"]
+    assert C.rnnx_members(1760, relu) == 28 and RNN._bptt_cus(p) == 224
     assert RNN.make_xcd_plan(64, 1760, "rnn_relu", 2, 256) is None          # R = 16 > 8
-    assert not RNN._wide_ok(1760, "gru") and not RNN._wide_ok(1024, "rnn_relu")
-    assert RNN._wide_ok(1056, "rnn_relu") and not RNN._wide_ok(1824, "rnn_relu")
+    assert C.rnnx_fwd_family(1760, gru, 0) != 6 and C.rnnx_fwd_family(1024, relu, 0) != 6
+    assert C.rnnx_fwd_family(1056, relu, 0) == 6 and C.rnnx_fwd_family(1824, relu, 0) != 6
     head = RNN.make_xcd_plan(32, 800, "gru", 2, 256)                        # headline: 200 CUs
     c5 = RNN.make_xcd_plan(32, 1280, "gru", 2, 256)                         # config 5: 160 CUs
     assert RNN._bptt_cus(head) == 200 and RNN._bptt_cus(c5) == 160
@@ -211,8 +212,38 @@ def test_recurrence_kernel_family_map():
         assert bw.startswith({"rnnw_fwd": "rnnw_bwd"}.get(fam, "rnn_bwd" if fam.startswith("rnn_fwd") else "rnnrs_bwd"))
     # the timing-only knob bits never reach the family choice, the selector bit 256 does
     p = RNN.make_plan(32, 800, "gru", 2, 256)
-    assert int(RNN._ext.ext().rnnx_fwd_family(800, 1, 1, 256)) == 2
+    assert int(RNN._ext.ext().rnnx_fwd_family(800, 1, 256)) == 2
     assert RNN.kernel_families(p)[0].startswith("rnne_fwd")
+
+
+def test_xcd_plans_agree_with_the_extension():
+    """make_xcd_plan builds its plans from what csrc/rnn_xcd.hip reports (rnnx_members,
+    rnnx_fwd_family, rnnx_bwd_family): over both cells, 1 / 2 directions, 128 / 256 / 304 CUs,
+    H = 32..2048 in steps of 32 and 12 batch sizes, every plan it returns is one the dispatch
+    accepts, fits the chip with the grid the launch will use, and is wide exactly where the
+    kernels use 64-unit groups (no GPU needed)."""
+    from deepspeech_amd.ops import rnn as RNN
+    C = RNN._ext.ext()
+    plans = 0
+    for cell, code in RNN.CELL_CODE.items():
+        for H in range(32, 2049, 32):
+            P = int(C.rnnx_members(H, code))
+            for ndir in (1, 2):
+                for cus in (128, 256, 304):
+                    for N in (1, 2, 3, 5, 8, 12, 16, 24, 32, 48, 64, 128):
+                        p = RNN.make_xcd_plan(N, H, cell, ndir, cus)
+                        if p is None:
+                            continue
+                        plans += 1
+                        fam = int(C.rnnx_fwd_family(H, code, RNN._kernel_knobs(p)))
+                        assert fam != 0 and int(C.rnnx_bwd_family(H, code, p.R)) != 0, p
+                        ngroups = ndir * p.BG
+                        grid = int(C.rnnx_grid(H, code, ngroups, p.xcd_map))
+                        assert grid == (8 * P if p.xcd_map and ngroups <= 8 else ngroups * P), p
+                        assert 0 < grid <= cus, p
+                        assert p.NP == p.BG * p.R >= N and p.mt == 1, p
+                        assert (fam == 6) == (P == -(-H // 64) != H // 32), p
+    assert plans > 5000
 
 
 @pytest.mark.parametrize("name,N,H,cell,T,dp,fp8,want", [
