@@ -173,6 +173,11 @@ def build_eval_parser() -> argparse.ArgumentParser:
     p.add_argument("--dummy", type=str2bool, default=False, help="evaluate on synthetic data")
     p.add_argument("--decoder", type=str, default="greedy", choices=["greedy", "beam"])
     p.add_argument("--beam_width", type=int, default=16)
+    p.add_argument("--lm_path", type=str, default="",
+                   help="character n-gram LM for --decoder beam: ARPA text or compiled .npz (deepspeech_amd/lm.py)")
+    p.add_argument("--lm_weight", type=float, default=1.0, help="LM weight alpha of the shallow fusion")
+    p.add_argument("--label_bonus", type=float, default=0.0, help="per-label bonus beta (nats)")
+    p.add_argument("--report_wer", type=str2bool, default=False, help="also report the word error rate")
     p.add_argument("--use_ema", type=str2bool, default=True,
                    help="evaluate the EMA (shadow) weights like the reference")
     p.add_argument("--num_examples", type=int, default=0, help="override eval set size")

@@ -199,6 +199,15 @@ int ds2_ctc_beam(const float* lp, const int* frames, int T, int B, int K, int W,
 int ds2_ctc_beam_backtrack(const void* nodes, int cap, const int* node, const int* nbeam, const float* pb,
                            const float* pnb, int B, int W, int* out, int* out_len, float* score, int Lcap,
                            hipStream_t st);
+// LM shallow fusion: lm [S][K] int2 rows (w fp32 bits, next state), lmstate [B][W] int32, lmkey
+// [B][W][2] 64-bit prefix fingerprints (own, parent's; zero at reset); the backtrack adds the
+// </s> weight (column blank) to every score (final mode). -51: bad LM arguments.
+int ds2_ctc_beam_lm(const float* lp, const int* frames, int T, int B, int K, int W, int blank, float prune, int* node,
+                    int* last, int* parent, float* pb, float* pnb, int* nbeam, void* nodes, int* nnodes, int cap,
+                    unsigned* err, const void* lm, int S, int* lmstate, unsigned long long* lmkey, hipStream_t st);
+int ds2_ctc_beam_backtrack_lm(const void* nodes, int cap, const int* node, const int* nbeam, const float* pb,
+                              const float* pnb, int B, int W, int* out, int* out_len, float* score, int Lcap,
+                              const void* lm, int S, int K, int blank, const int* lmstate, hipStream_t st);
 
 // ---- align.hip --------------------------------------------------------------------------
 // CTC forced alignment (Viterbi path + backtrack). em [T, N, K] fp32 / bf16 (log_probs != 0: used

@@ -22,6 +22,25 @@
 // so the float results do not depend on accumulation order; they equal the host decoder's up
 // to the ulps of expf / log1pf. Reference semantics: tf.nn.ctc_beam_search_decoder (the
 // reference itself decodes greedily, src/deepSpeech_test.py:212-215).
+//
+// Shallow LM fusion (ctc_beam_kernel<true>; deepspeech_amd/lm.py): the LM is a backoff-expanded
+// automaton packed as int2 rows lm[state][k] = (w, next) with w = alpha * ln P(k | state) + beta
+// as fp32 bits. Each hypothesis carries its state in a lane register beside its node; at the top
+// of a frame lane k loads row state_j, column k for every live j (W coalesced 8-byte loads whose
+// latency overlaps the merge scan and the frame's own log-prob load), every extension term gets
+// (base + p) + w, and when (j, k) is selected the survivor's state is a readlane of the `next`
+// lane k already holds: nothing loads inside the serial selection. The <false> instantiation is
+// the acoustic search as it was.
+//
+// Prefix identity with an LM. The node-id test above ("parent(i) == node(j)") assumes that a live
+// prefix has one trie node. That breaks when a prefix P is pruned while a longer Q = P + x stays
+// live and P is then created again from its own parent: P gets a fresh node, Q still points to
+// the old one, the extension of P by x no longer finds Q and the beam holds Q twice. The acoustic
+// search meets this rarely; LM weights reorder the beam enough to meet it within 30 frames
+// (W = 8). So <true> identifies prefixes by a 64-bit fingerprint carried beside the LM state
+// (key of a prefix = mix(key of its parent, label), key of the empty prefix = 0) and compares
+// (key, parent key) where <false> compares (node, parent node): registers only, no loads. Two
+// different live prefixes one label apart collide with probability 2^-64 per comparison.
 #include "common.h"
 
 using namespace ds2;
@@ -52,11 +71,29 @@ struct BeamArgs {
   int* nnodes;         // [B] nodes used
   int cap;
   unsigned* err;       // bit 1: node table full (host sizes it: 1 + W * frames)
+  const int2* lm;      // LM only: [S][K] (w fp32 bits, next state; column blank: (w of </s>, -1))
+  int* lmstate;        // LM only: [B][W] LM state of each hypothesis
+  unsigned long long* lmkey;   // LM only: [B][W][2] fingerprint of each hypothesis' prefix and of its parent's
+  int S;
 };
+
+__device__ __forceinline__ unsigned long long bcast(unsigned long long v, int l) {
+  return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) |
+         (unsigned)__builtin_amdgcn_readlane((int)v, l);
+}
+
+// fingerprint of prefix + label (splitmix64 finaliser over parent key and label)
+__device__ __forceinline__ unsigned long long key_extend(unsigned long long parent, int label) {
+  unsigned long long x = parent + (unsigned long long)(label + 1) * 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
 
 __device__ __forceinline__ float bcast(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 __device__ __forceinline__ int bcast(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
 
+template <bool LM>
 __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -67,6 +104,15 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
   int nn = a.nnodes[b];
   int h_node = 0, h_last = -1, h_par = -1;
   float h_pb = -INFINITY, h_pnb = -INFINITY;
+  int h_state = 0;
+  unsigned long long h_key = 0ull, h_pkey = 0ull;
+  if constexpr (LM) {
+    if (lane < nb) {
+      h_state = min(max(a.lmstate[bo + lane], 0), a.S - 1);
+      h_key = a.lmkey[(bo + lane) * 2];
+      h_pkey = a.lmkey[(bo + lane) * 2 + 1];
+    }
+  }
   if (lane < nb) {
     h_node = a.node[bo + lane];
     h_last = a.last[bo + lane];
@@ -81,6 +127,18 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
       if (lane == 0) atomicOr(a.err, 1u);
       break;
     }
+    // lane k: (w, next) of every live hypothesis j's LM state for class k
+    int2 wn[LM ? BM_MAXW : 1];
+    if constexpr (LM) {
+#pragma unroll
+      for (int j = 0; j < BM_MAXW; ++j) {
+        wn[j] = make_int2(0, 0);
+        if (j < nb) {
+          const int sj = bcast(h_state, j);
+          if (lane < K) wn[j] = a.lm[(size_t)sj * K + lane];
+        }
+      }
+    }
     const float p = lane < K ? a.lp[((size_t)t * a.B + b) * K + lane] : -INFINITY;
     float mx = p;
 #pragma unroll
@@ -94,8 +152,20 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
     unsigned long long mmask = 0ull;
     for (int i = 0; i < nb; ++i) {
       const int ni = bcast(h_node, i), pi = bcast(h_par, i), li = bcast(h_last, i);
-      if (live && h_par >= 0 && ni == h_par) msrc = i;
-      if (pi >= 0 && pi == h_node && live) mmask |= 1ull << li;
+      if constexpr (LM) {
+        const unsigned long long ki = bcast(h_key, i), pki = bcast(h_pkey, i);
+        if (live && h_par >= 0 && ki == h_pkey) msrc = i;
+        if (pi >= 0 && pki == h_key && live) mmask |= 1ull << li;
+      } else {
+        if (live && h_par >= 0 && ni == h_par) msrc = i;
+        if (pi >= 0 && pi == h_node && live) mmask |= 1ull << li;
+      }
+    }
+    // LM weight of the merged extension: row state(msrc), column my last label
+    float m_w = 0.f;
+    if constexpr (LM) {
+      const int m_state = __shfl(h_state, msrc >= 0 ? msrc : 0, 64);
+      if (msrc >= 0 && h_last >= 0) m_w = __int_as_float(a.lm[(size_t)m_state * K + h_last].x);
     }
     // stay entry of my hypothesis: blank, a repeat of the last label, and the merged extension
     const float pblank = __shfl(p, a.blank, 64);
@@ -108,7 +178,11 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
       if ((cmask >> a.blank) & 1ull) s_pb = tot + pblank;
       if (h_last >= 0 && ((cmask >> h_last) & 1ull)) {
         s_pnb = h_pnb + plast;
-        if (msrc >= 0) s_pnb = log_add(s_pnb, (m_last == h_last ? m_pb : m_tot) + plast);
+        if constexpr (LM) {
+          if (msrc >= 0) s_pnb = log_add(s_pnb, ((m_last == h_last ? m_pb : m_tot) + plast) + m_w);
+        } else {
+          if (msrc >= 0) s_pnb = log_add(s_pnb, (m_last == h_last ? m_pb : m_tot) + plast);
+        }
       }
     }
     float stay = live ? log_add(s_pb, s_pnb) : -INFINITY;
@@ -123,13 +197,19 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
         const int lj = bcast(h_last, j);
         const unsigned long long mj = ((unsigned long long)(unsigned)bcast((int)(mmask >> 32), j) << 32) |
                                       (unsigned)bcast((int)mmask, j);
-        if (kc && !((mj >> lane) & 1ull)) ext[j] = (lane == lj ? pj : tj) + p;
+        if constexpr (LM) {
+          if (kc && !((mj >> lane) & 1ull)) ext[j] = ((lane == lj ? pj : tj) + p) + __int_as_float(wn[j].x);
+        } else {
+          if (kc && !((mj >> lane) & 1ull)) ext[j] = (lane == lj ? pj : tj) + p;
+        }
       }
     }
     // top-W: stays have ids 0..W-1, extension (j, k) id W + j * 64 + k
     int nsel = 0, newn = 0;
     int n_node = 0, n_last = -1, n_par = -1;
     float n_pb = -INFINITY, n_pnb = -INFINITY;
+    int n_state = 0;
+    unsigned long long n_key = 0ull, n_pkey = 0ull;
     for (int r = 0; r < W; ++r) {
       float best = stay;
       int bid = live ? lane : 0x7fffffff;
@@ -156,6 +236,15 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
         if (lane == j) stay = -INFINITY;
         const int nj = bcast(h_node, j), lj = bcast(h_last, j), pj = bcast(h_par, j);
         const float bj = bcast(s_pb, j), qj = bcast(s_pnb, j);
+        if constexpr (LM) {
+          const int sj = bcast(h_state, j);            // a stay keeps its state and keys
+          const unsigned long long kj = bcast(h_key, j), pkj = bcast(h_pkey, j);
+          if (lane == r) {
+            n_state = sj;
+            n_key = kj;
+            n_pkey = pkj;
+          }
+        }
         if (lane == r) {
           n_node = nj;
           n_last = lj;
@@ -169,6 +258,19 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
 #pragma unroll
           for (int q = 0; q < BM_MAXW; ++q)
             if (q == j) ext[q] = -INFINITY;
+        }
+        if constexpr (LM) {
+          int nx = 0;
+#pragma unroll
+          for (int q = 0; q < BM_MAXW; ++q)
+            if (q == j) nx = wn[q].y;
+          const int sk = min(max(bcast(nx, k), 0), a.S - 1);   // lane k holds next(state_j, k)
+          const unsigned long long kj = bcast(h_key, j);
+          if (lane == r) {
+            n_state = sk;
+            n_key = key_extend(kj, k);
+            n_pkey = kj;
+          }
         }
         const int nj = bcast(h_node, j);
         const int id = nn + newn;
@@ -191,6 +293,18 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
     h_par = n_par;
     h_pb = n_pb;
     h_pnb = n_pnb;
+    if constexpr (LM) {
+      h_state = n_state;
+      h_key = n_key;
+      h_pkey = n_pkey;
+    }
+  }
+  if constexpr (LM) {
+    if (lane < W) {
+      a.lmstate[bo + lane] = h_state;
+      a.lmkey[(bo + lane) * 2] = h_key;
+      a.lmkey[(bo + lane) * 2 + 1] = h_pkey;
+    }
   }
   if (lane < W) {
     a.node[bo + lane] = h_node;
@@ -206,11 +320,13 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
 }
 
 // labels of every live hypothesis: out [B][W][Lcap] (reversed walk written back to front),
-// out_len [B][W] (-1: no such hypothesis), score [B][W] = log_add(pb, pnb)
+// out_len [B][W] (-1: no such hypothesis), score [B][W] = log_add(pb, pnb); with lm (final
+// mode) plus the </s> weight of the hypothesis' LM state, lm[state][eos].x
 __global__ __launch_bounds__(64) void ctc_beam_backtrack_kernel(const int2* nodes, int cap, const int* node,
                                                                   const int* nbeam, const float* pb, const float* pnb,
                                                                   int B, int W, int* out, int* out_len, float* score,
-                                                                  int Lcap) {
+                                                                  int Lcap, const int2* lm, const int* lmstate, int S,
+                                                                  int K, int eos) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= B * W) return;
   const int b = i / W, h = i - b * W;
@@ -226,7 +342,9 @@ __global__ __launch_bounds__(64) void ctc_beam_backtrack_kernel(const int2* node
   int pos = L;
   for (int n = node[i]; n > 0 && pos > 0; n = tab[n].x) out[(size_t)i * Lcap + --pos] = tab[n].y;
   out_len[i] = L;
-  score[i] = log_add(pb[i], pnb[i]);
+  float sc = log_add(pb[i], pnb[i]);
+  if (lm != nullptr) sc += __int_as_float(lm[(size_t)min(max(lmstate[i], 0), S - 1) * K + eos].x);
+  score[i] = sc;
 }
 
 }  // namespace
@@ -237,8 +355,24 @@ extern "C" int ds2_ctc_beam(const float* lp, const int* frames, int T, int B, in
   if (K < 2 || K > 64 || W < 1 || W > BM_MAXW || blank < 0 || blank >= K || B < 1 || T < 0 || cap < 1) return -50;
   if (T == 0) return 0;
   BeamArgs a{lp, frames, T, B, K, W, blank, prune, node, last, parent, pb, pnb, nbeam,
-             static_cast<int2*>(nodes), nnodes, cap, err};
-  ds2_launch(ctc_beam_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a);
+             static_cast<int2*>(nodes), nnodes, cap, err, nullptr, nullptr, nullptr, 0};
+  ds2_launch(ctc_beam_kernel<false>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a);
+  return (int)hipGetLastError();
+}
+
+// the same search with the LM automaton lm [S][K] int2, the per-hypothesis states lmstate [B][W]
+// and prefix fingerprints lmkey [B][W][2]
+extern "C" int ds2_ctc_beam_lm(const float* lp, const int* frames, int T, int B, int K, int W, int blank, float prune,
+                               int* node, int* last, int* parent, float* pb, float* pnb, int* nbeam, void* nodes,
+                               int* nnodes, int cap, unsigned* err, const void* lm, int S, int* lmstate,
+                               unsigned long long* lmkey, hipStream_t st) {
+  if (K < 2 || K > 64 || W < 1 || W > BM_MAXW || blank < 0 || blank >= K || B < 1 || T < 0 || cap < 1) return -50;
+  if (lm == nullptr || lmstate == nullptr || lmkey == nullptr || S < 1 || (long long)S * K >= (1ll << 31))
+    return -51;
+  if (T == 0) return 0;
+  BeamArgs a{lp, frames, T, B, K, W, blank, prune, node, last, parent, pb, pnb, nbeam,
+             static_cast<int2*>(nodes), nnodes, cap, err, static_cast<const int2*>(lm), lmstate, lmkey, S};
+  ds2_launch(ctc_beam_kernel<true>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a);
   return (int)hipGetLastError();
 }
 
@@ -247,6 +381,20 @@ extern "C" int ds2_ctc_beam_backtrack(const void* nodes, int cap, const int* nod
                                       hipStream_t st) {
   if (B < 1 || W < 1 || Lcap < 1) return -50;
   ds2_launch(ctc_beam_backtrack_kernel, dim3((unsigned)((B * W + 63) / 64)), dim3(64), 0, st,
-             static_cast<const int2*>(nodes), cap, node, nbeam, pb, pnb, B, W, out, out_len, score, Lcap);
+             static_cast<const int2*>(nodes), cap, node, nbeam, pb, pnb, B, W, out, out_len, score, Lcap,
+             static_cast<const int2*>(nullptr), static_cast<const int*>(nullptr), 0, 0, 0);
+  return (int)hipGetLastError();
+}
+
+// final mode: score additionally gets the </s> weight lm[lmstate][blank].x (the host sorts again)
+extern "C" int ds2_ctc_beam_backtrack_lm(const void* nodes, int cap, const int* node, const int* nbeam,
+                                         const float* pb, const float* pnb, int B, int W, int* out, int* out_len,
+                                         float* score, int Lcap, const void* lm, int S, int K, int blank,
+                                         const int* lmstate, hipStream_t st) {
+  if (B < 1 || W < 1 || Lcap < 1) return -50;
+  if (lm == nullptr || lmstate == nullptr || S < 1 || K < 2 || blank < 0 || blank >= K) return -51;
+  ds2_launch(ctc_beam_backtrack_kernel, dim3((unsigned)((B * W + 63) / 64)), dim3(64), 0, st,
+             static_cast<const int2*>(nodes), cap, node, nbeam, pb, pnb, B, W, out, out_len, score, Lcap,
+             static_cast<const int2*>(lm), lmstate, S, K, blank);
   return (int)hipGetLastError();
 }

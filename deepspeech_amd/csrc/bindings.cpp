@@ -873,6 +873,75 @@ void ctc_beam_backtrack(at::Tensor node, at::Tensor last, at::Tensor parent, at:
         "ctc_beam_backtrack");
 }
 
+// LM shallow fusion (deepspeech_amd/lm.py): lm [S, K, 2] int32 (w fp32 bits, next state),
+// lmstate [B, W] int32 and lmkey [B, W, 2] int64 (prefix fingerprints) beside the beam state
+static void beam_lm_check(const at::Tensor& lm, const at::Tensor& lmstate, const at::Tensor& node, int64_t K) {
+  need_gpu(lm, "lm");
+  need_gpu(lmstate, "lmstate");
+  TORCH_CHECK(lm.dim() == 3 && lm.size(2) == 2 && lm.size(1) == K && lm.size(0) >= 1 &&
+                  lm.scalar_type() == at::kInt && lm.is_contiguous() && lm.size(0) * K < (1ll << 31),
+              "beam lm: contiguous int32 [S, K, 2], S * K < 2^31");
+  TORCH_CHECK(lmstate.scalar_type() == at::kInt && lmstate.is_contiguous() && lmstate.sizes() == node.sizes(),
+              "beam lm: lmstate int32 [B, W]");
+}
+
+void ctc_beam_lm(at::Tensor lp, OptT frames, int64_t blank, double prune, at::Tensor node, at::Tensor last,
+                 at::Tensor parent, at::Tensor pb, at::Tensor pnb, at::Tensor nbeam, at::Tensor nodes,
+                 at::Tensor nnodes, at::Tensor err, at::Tensor lm, at::Tensor lmstate, at::Tensor lmkey) {
+  need_gpu(lp, "lp");
+  TORCH_CHECK(lp.dim() == 3 && lp.scalar_type() == at::kFloat && lp.is_contiguous(),
+              "ctc_beam_lm: lp must be contiguous fp32 [T, B, K]");
+  const int64_t T = lp.size(0), B = lp.size(1), K = lp.size(2);
+  TORCH_CHECK(K >= 2 && K <= 64 && blank >= 0 && blank < K, "ctc_beam_lm: 2 <= K <= 64, 0 <= blank < K");
+  beam_state_check(node, last, parent, pb, pnb, nbeam, nodes, nnodes, B);
+  beam_lm_check(lm, lmstate, node, K);
+  need_gpu(lmkey, "lmkey");
+  TORCH_CHECK(lmkey.scalar_type() == at::kLong && lmkey.is_contiguous() && lmkey.dim() == 3 &&
+                  lmkey.size(0) == B && lmkey.size(1) == node.size(1) && lmkey.size(2) == 2,
+              "ctc_beam_lm: lmkey int64 [B, W, 2]");
+  need_gpu(err, "err");
+  TORCH_CHECK(err.scalar_type() == at::kInt && err.numel() >= 1, "ctc_beam_lm: err int32 [1]");
+  const int* fr = nullptr;
+  if (frames) {
+    need_gpu(*frames, "frames");
+    TORCH_CHECK(frames->scalar_type() == at::kInt && frames->is_contiguous() && frames->numel() == B,
+                "ctc_beam_lm: frames int32 [B]");
+    fr = frames->data_ptr<int>();
+  }
+  check(ds2_ctc_beam_lm(lp.data_ptr<float>(), fr, (int)T, (int)B, (int)K, (int)node.size(1), (int)blank,
+                        (float)prune, node.data_ptr<int>(), last.data_ptr<int>(), parent.data_ptr<int>(),
+                        pb.data_ptr<float>(), pnb.data_ptr<float>(), nbeam.data_ptr<int>(), nodes.data_ptr(),
+                        nnodes.data_ptr<int>(), (int)nodes.size(1), reinterpret_cast<unsigned*>(err.data_ptr<int>()),
+                        lm.data_ptr(), (int)lm.size(0), lmstate.data_ptr<int>(),
+                        reinterpret_cast<unsigned long long*>(lmkey.data_ptr<int64_t>()), cur_stream()),
+        "ctc_beam_lm");
+}
+
+// ctc_beam_backtrack with the </s> weight of each hypothesis' LM state added to its score
+void ctc_beam_backtrack_lm(at::Tensor node, at::Tensor last, at::Tensor parent, at::Tensor pb, at::Tensor pnb,
+                           at::Tensor nbeam, at::Tensor nodes, at::Tensor nnodes, at::Tensor out, at::Tensor out_len,
+                           at::Tensor score, at::Tensor lm, at::Tensor lmstate, int64_t blank) {
+  const int64_t B = node.size(0), W = node.size(1);
+  beam_state_check(node, last, parent, pb, pnb, nbeam, nodes, nnodes, B);
+  TORCH_CHECK(lm.dim() == 3, "beam lm: contiguous int32 [S, K, 2]");
+  const int64_t K = lm.size(1);
+  beam_lm_check(lm, lmstate, node, K);
+  TORCH_CHECK(blank >= 0 && blank < K, "ctc_beam_backtrack_lm: 0 <= blank < K");
+  need_gpu(out, "out");
+  need_gpu(out_len, "out_len");
+  need_gpu(score, "score");
+  TORCH_CHECK(out.dim() == 3 && out.size(0) == B && out.size(1) == W && out.scalar_type() == at::kInt &&
+                  out.is_contiguous(), "ctc_beam_backtrack_lm: out int32 [B, W, L]");
+  TORCH_CHECK(out_len.numel() == B * W && out_len.scalar_type() == at::kInt && out_len.is_contiguous() &&
+                  score.numel() == B * W && score.scalar_type() == at::kFloat && score.is_contiguous(),
+              "ctc_beam_backtrack_lm: out_len int32 / score fp32 [B, W]");
+  check(ds2_ctc_beam_backtrack_lm(nodes.data_ptr(), (int)nodes.size(1), node.data_ptr<int>(), nbeam.data_ptr<int>(),
+                                  pb.data_ptr<float>(), pnb.data_ptr<float>(), (int)B, (int)W, out.data_ptr<int>(),
+                                  out_len.data_ptr<int>(), score.data_ptr<float>(), (int)out.size(2), lm.data_ptr(),
+                                  (int)lm.size(0), (int)K, (int)blank, lmstate.data_ptr<int>(), cur_stream()),
+        "ctc_beam_backtrack_lm");
+}
+
 // out[k] (= or +=) scale[0] * alpha * sum_m G[m, k] for k < K (G bf16 [M, ldg] with unit column
 // stride, scale a device fp32 scalar): the FC head's bias gradient (csrc/reduce.hip)
 void fc_bias_grad(at::Tensor G, int64_t K, at::Tensor scale, double alpha, at::Tensor out, bool acc) {
@@ -1377,6 +1446,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("fc_bias_grad", &fc_bias_grad);
   m.def("ctc_beam", &ctc_beam);
   m.def("ctc_beam_backtrack", &ctc_beam_backtrack);
+  m.def("ctc_beam_lm", &ctc_beam_lm);
+  m.def("ctc_beam_backtrack_lm", &ctc_beam_backtrack_lm);
   m.def("event_new", &event_new, py::arg("flags") = 0);
   m.def("arm_stop_event", &arm_stop_event);
   m.def("disarm_stop_event", &disarm_stop_event);

@@ -44,7 +44,10 @@ def frames_out(T: int) -> int:
 
 class StreamingRecognizer:
     def __init__(self, model: DeepSpeech2, decoder: str = "greedy", beam_width: int = 16, batch: int = 1,
-                 graphs: Optional[bool] = None, features: str = "mfcc", audio_gain: Optional[float] = None):
+                 graphs: Optional[bool] = None, features: str = "mfcc", audio_gain: Optional[float] = None,
+                 lm=None, lm_weight: float = 1.0, label_bonus: float = 0.0):
+        """``lm`` (a deepspeech_amd.lm.CharNgramLM, beam decoder only): shallow fusion with weight
+        ``lm_weight`` and a per-label bonus ``label_bonus`` (ops/decode.py)."""
         if model.bidirectional:
             raise ValueError("streaming needs a unidirectional model (rnn_type='uni-dir')")
         # accept_audio(): PCM is featurized on the model's device (ops/featurize.py) with a fixed
@@ -56,6 +59,9 @@ class StreamingRecognizer:
         self.model = model.eval()
         self.decoder = decoder
         self.beam_width = beam_width
+        if lm is not None and decoder != "beam":
+            raise ValueError("a language model needs decoder='beam'")
+        self.lm, self.lm_weight, self.label_bonus = lm, float(lm_weight), float(label_bonus)
         self.B = batch
         self.dev = model.fc_weight.device
         # HIP graphs: a chunk's ~40 launches (conv front-end, 5 x (projection GEMM, sentinel
@@ -84,10 +90,17 @@ class StreamingRecognizer:
         if self.decoder == "beam":
             from .ops.decode import GpuBeamSearch
             if self.dev.type == "cuda" and self.beam_width <= GpuBeamSearch.MAX_BEAM:
-                self.gbeams = GpuBeamSearch(self.B, self.beam_width, BLANK, -10.0, self.dev)
-            else:
+                self.gbeams = GpuBeamSearch(self.B, self.beam_width, BLANK, -10.0, self.dev, lm=self.lm,
+                                            lm_weight=self.lm_weight, label_bonus=self.label_bonus)
+            elif self.lm is None:
                 from .runtime import native
                 self.beams = native.load().BatchBeamSearch(self.B, self.beam_width, BLANK, -10.0)
+            else:
+                from .ops.decode import host_lm
+                from .runtime import native
+                self.beams = native.load().BatchBeamSearch(
+                    self.B, self.beam_width, BLANK, -10.0,
+                    lm=host_lm(self.lm, self.lm_weight, self.label_bonus, BLANK))
         self.last_sym = [-1] * self.B
         self.greedy: List[List[int]] = [[] for _ in range(self.B)]
         self.compute_s = 0.0
@@ -229,12 +242,14 @@ class StreamingRecognizer:
     @torch.no_grad()
     def finish(self) -> List[List[int]]:
         """Final transcript label ids per stream (beam search over the whole stream if the
-        decoder is 'beam', otherwise the incremental greedy result)."""
+        decoder is 'beam', otherwise the incremental greedy result). With an LM the streams
+        end here: the end-of-sentence term counts."""
+        final = self.lm is not None
         if self.gbeams is not None:
-            return self.gbeams.best()
+            return self.gbeams.best(final) if final else self.gbeams.best()
         if self.beams is None:
             return [list(g) for g in self.greedy]
-        return self.beams.best()
+        return self.beams.best(final) if final else self.beams.best()
 
     @torch.no_grad()
     def finish_timed(self):
@@ -258,16 +273,18 @@ class StreamingRecognizer:
 
 
 def rtf(model: DeepSpeech2, seconds: float = 10.0, chunk_s: float = 1.0, batch: int = 1,
-        decoder: str = "greedy", beam_width: int = 16, seed: int = 0, audio: bool = False):
+        decoder: str = "greedy", beam_width: int = 16, seed: int = 0, audio: bool = False, lm=None,
+        lm_weight: float = 1.0, label_bonus: float = 0.0):
     """Real-time factor of streaming synthetic audio: compute time / audio time (per stream;
     ``batch`` streams are processed together). Returns (rtf, transcripts). ``audio=True`` streams
     synthetic int16 PCM through accept_audio() (featurization included in the compute time)
-    instead of ready-made feature frames."""
+    instead of ready-made feature frames. ``lm``: a CharNgramLM fused into the beam decoder."""
     g = torch.Generator().manual_seed(seed)
+    lmkw = {} if lm is None else dict(lm=lm, lm_weight=lm_weight, label_bonus=label_bonus)
     if audio:
         n = int(round(seconds * 16000))
         pcm = (torch.randn(batch, n, generator=g) * 3000.0).clamp_(-32768, 32767).to(torch.int16)
-        rec = StreamingRecognizer(model, decoder=decoder, beam_width=beam_width, batch=batch)
+        rec = StreamingRecognizer(model, decoder=decoder, beam_width=beam_width, batch=batch, **lmkw)
         step = max(1, int(round(chunk_s * 16000)))
         for s in range(0, n, step):
             rec.accept_audio(pcm[:, s:s + step], final=s + step >= n)
@@ -275,7 +292,7 @@ def rtf(model: DeepSpeech2, seconds: float = 10.0, chunk_s: float = 1.0, batch: 
         return rec.compute_s / seconds, res
     T = int(round(seconds * 100))
     feats = torch.randn(batch, T, model.freq_bins, generator=g)
-    rec = StreamingRecognizer(model, decoder=decoder, beam_width=beam_width, batch=batch)
+    rec = StreamingRecognizer(model, decoder=decoder, beam_width=beam_width, batch=batch, **lmkw)
     step = max(1, int(round(chunk_s * 100)))
     for s in range(0, T, step):
         rec.accept(feats[:, s:s + step])

@@ -5,7 +5,9 @@ greedy: csrc/decode.hip on the GPU (argmax + merge repeats + drop blank + path s
         plain PyTorch (ops/reference.py) on the CPU.
 beam:   CTC prefix beam search: csrc/beam.hip on the GPU (beams resident on the device, one
         wave64 per utterance / stream, GpuBeamSearch), the native host runtime
-        (runtime/decoder.cpp, one thread per utterance) on the CPU.
+        (runtime/decoder.cpp, one thread per utterance) on the CPU. Both take a character
+        n-gram LM (deepspeech_amd/lm.py CharNgramLM) for shallow fusion: a prefix l_1..l_n is
+        ranked by log P_ctc + lm_weight * ln P_lm(l_1..l_n) + label_bonus * n.
 """
 from __future__ import annotations
 
@@ -45,17 +47,42 @@ def greedy_decode(logits: torch.Tensor, lens: torch.Tensor, blank: int = BLANK,
     return out, sc
 
 
+def lm_tables(lm, lm_weight: float, label_bonus: float, blank: int, K: int = None):
+    """(folded fp32 [S, K], nxt int32 [S, K], start) of a CharNgramLM for a decoder with this
+    blank (and class count, when known)."""
+    if lm.blank != blank or (K is not None and lm.K != K):
+        raise ValueError("beam search: the LM is over %d classes with blank %d, the decoder has %s with blank %d"
+                         % (lm.K, lm.blank, "?" if K is None else K, blank))
+    _, nxt, start = lm.compile()
+    return lm.fold(lm_weight, label_bonus), nxt, start
+
+
+def host_lm(lm, lm_weight: float = 1.0, label_bonus: float = 0.0, blank: int = BLANK):
+    """The native runtime's shared LM object (runtime/decoder.cpp BeamLM), None without an LM."""
+    if lm is None:
+        return None
+    from ..runtime import native
+    w, nxt, start = lm_tables(lm, lm_weight, label_bonus, blank)
+    return native.load().BeamLM(w, nxt, start, blank)
+
+
 def beam_decode(logits: torch.Tensor, lens: torch.Tensor, beam_width: int = 16, blank: int = BLANK,
-                prune: float = -10.0) -> List[List[int]]:
-    """logits [T, N, K] time-major -> the best prefix of each utterance's beam search."""
+                prune: float = -10.0, lm=None, lm_weight: float = 1.0,
+                label_bonus: float = 0.0) -> List[List[int]]:
+    """logits [T, N, K] time-major -> the best prefix of each utterance's beam search (with an
+    LM: of the whole utterance, the end-of-sentence term included)."""
     if logits.is_cuda and beam_width <= GpuBeamSearch.MAX_BEAM:
         T, N, _ = logits.shape
-        bs = GpuBeamSearch(N, beam_width, blank, prune, logits.device, frames_hint=T)
+        bs = GpuBeamSearch(N, beam_width, blank, prune, logits.device, frames_hint=T, lm=lm,
+                           lm_weight=lm_weight, label_bonus=label_bonus)
         bs.feed(torch.log_softmax(logits.float(), dim=-1), lens)
-        return bs.best()
+        return bs.best(final=lm is not None)
     from ..runtime import native
     lp = torch.log_softmax(logits.float(), dim=-1).cpu().numpy()
-    return native.load().beam_search_batch(lp, lens.cpu().numpy().astype(np.int32), beam_width, blank, prune)
+    if lm is None:
+        return native.load().beam_search_batch(lp, lens.cpu().numpy().astype(np.int32), beam_width, blank, prune)
+    return native.load().beam_search_batch(lp, lens.cpu().numpy().astype(np.int32), beam_width, blank, prune,
+                                           lm=host_lm(lm, lm_weight, label_bonus, blank), final=True)
 
 
 class GpuBeamSearch:
@@ -64,11 +91,14 @@ class GpuBeamSearch:
     one launch on the current stream (no host synchronisation, so a streaming recogniser feeds
     each chunk straight from its log-softmax), :meth:`results` / :meth:`best` walk the trie on
     the device and read the prefixes back once. Same search as runtime/decoder.cpp
-    PrefixBeamSearch (prune window, blank / repeat rules, merged prefixes)."""
+    PrefixBeamSearch (prune window, blank / repeat rules, merged prefixes), with the same
+    shallow LM fusion when ``lm`` (a CharNgramLM) is given: the folded table goes to the device
+    once, and each hypothesis carries its LM state beside its trie node."""
     MAX_BEAM = 32
 
     def __init__(self, streams: int, beam: int, blank: int = BLANK, prune: float = -10.0,
-                 device: torch.device = None, frames_hint: int = 256):
+                 device: torch.device = None, frames_hint: int = 256, lm=None, lm_weight: float = 1.0,
+                 label_bonus: float = 0.0):
         if not 1 <= beam <= self.MAX_BEAM:
             raise ValueError("GpuBeamSearch: 1 <= beam <= %d" % self.MAX_BEAM)
         self.B, self.W, self.blank, self.prune = int(streams), int(beam), int(blank), float(prune)
@@ -85,6 +115,19 @@ class GpuBeamSearch:
         self.nnodes = torch.empty(self.B, **i32)
         self.nodes = torch.zeros(self.B, self.cap, 2, **i32)
         self.err = torch.zeros(1, **i32)
+        self.lm = None
+        if lm is not None:
+            w, nxt, start = lm_tables(lm, lm_weight, label_bonus, self.blank)
+            S = w.shape[0]
+            lab = np.delete(nxt, self.blank, axis=1)
+            if not 0 <= start < S or lab.min() < 0 or lab.max() >= S:
+                raise ValueError("GpuBeamSearch: LM next-state table outside [0, S)")
+            packed = np.stack([w.view(np.int32), nxt], axis=-1)                 # [S, K, 2]: (w bits, next)
+            self.lm = torch.from_numpy(np.ascontiguousarray(packed)).to(self.dev)
+            self.lm_start = int(start)
+            self.lmstate = torch.empty(self.B, self.W, **i32)
+            # 64-bit fingerprints of each hypothesis' prefix and of its parent's (csrc/beam.hip)
+            self.lmkey = torch.empty(self.B, self.W, 2, device=self.dev, dtype=torch.int64)
         self.reset()
 
     def reset(self) -> None:
@@ -97,6 +140,9 @@ class GpuBeamSearch:
         self.pnb.fill_(float("-inf"))
         self.nbeam.fill_(1)
         self.nnodes.fill_(1)
+        if self.lm is not None:
+            self.lmstate.fill_(self.lm_start)
+            self.lmkey.zero_()
         self.frames = 0          # frames fed so far (upper bound over streams): sizes the trie
 
     def _ensure(self, more: int) -> None:
@@ -125,24 +171,42 @@ class GpuBeamSearch:
         elif frames is not None:
             fr = frames.to(device=self.dev, dtype=torch.int32).contiguous()
         self._ensure(T)
-        _ext.ext().ctc_beam(lp, fr, self.blank, self.prune, self.node, self.last, self.parent, self.pb,
-                            self.pnb, self.nbeam, self.nodes, self.nnodes, self.err)
+        if self.lm is not None:
+            if lp.shape[2] != self.lm.shape[1]:
+                raise ValueError("GpuBeamSearch.feed: lp has %d classes, the LM %d" % (lp.shape[2], self.lm.shape[1]))
+            _ext.ext().ctc_beam_lm(lp, fr, self.blank, self.prune, self.node, self.last, self.parent, self.pb,
+                                   self.pnb, self.nbeam, self.nodes, self.nnodes, self.err, self.lm, self.lmstate,
+                                   self.lmkey)
+        else:
+            _ext.ext().ctc_beam(lp, fr, self.blank, self.prune, self.node, self.last, self.parent, self.pb,
+                                self.pnb, self.nbeam, self.nodes, self.nnodes, self.err)
         self.frames += T
 
-    def results(self) -> List[List[Tuple[List[int], float]]]:
-        """Per stream, the live hypotheses best first: (labels, log p). Synchronises."""
+    def results(self, final: bool = False) -> List[List[Tuple[List[int], float]]]:
+        """Per stream, the live hypotheses best first: (labels, log p). ``final`` (with an LM):
+        the streams end here, so every score also gets lm_weight * ln P(</s> | prefix) and the
+        lists are sorted again. Synchronises."""
         from . import _ext
         L = max(1, self.frames)
         out = torch.empty(self.B, self.W, L, device=self.dev, dtype=torch.int32)
         out_len = torch.empty(self.B, self.W, device=self.dev, dtype=torch.int32)
         score = torch.empty(self.B, self.W, device=self.dev, dtype=torch.float32)
-        _ext.ext().ctc_beam_backtrack(self.node, self.last, self.parent, self.pb, self.pnb, self.nbeam,
-                                      self.nodes, self.nnodes, out, out_len, score)
+        eos = bool(final) and self.lm is not None
+        if eos:
+            _ext.ext().ctc_beam_backtrack_lm(self.node, self.last, self.parent, self.pb, self.pnb, self.nbeam,
+                                             self.nodes, self.nnodes, out, out_len, score, self.lm, self.lmstate,
+                                             self.blank)
+        else:
+            _ext.ext().ctc_beam_backtrack(self.node, self.last, self.parent, self.pb, self.pnb, self.nbeam,
+                                          self.nodes, self.nnodes, out, out_len, score)
         if int(self.err.item()) != 0:
             raise RuntimeError("GpuBeamSearch: trie node table overflow")
         o, n, s = out.cpu().numpy(), out_len.cpu().numpy(), score.cpu().numpy()
-        return [[(o[b, h, : n[b, h]].tolist(), float(s[b, h])) for h in range(self.W) if n[b, h] >= 0]
-                for b in range(self.B)]
+        res = [[(o[b, h, : n[b, h]].tolist(), float(s[b, h])) for h in range(self.W) if n[b, h] >= 0]
+               for b in range(self.B)]
+        if eos:
+            res = [sorted(r, key=lambda e: -e[1]) for r in res]     # stable: ties keep the beam order
+        return res
 
-    def best(self) -> List[List[int]]:
-        return [r[0][0] if r else [] for r in self.results()]
+    def best(self, final: bool = False) -> List[List[int]]:
+        return [r[0][0] if r else [] for r in self.results(final)]

@@ -56,7 +56,29 @@ def levenshtein(a, b) -> int:
         return prev[-1]
 
 
-def decode(logits: torch.Tensor, lens: torch.Tensor, decoder: str, beam_width: int) -> List[List[int]]:
+def word_errors(ref: str, hyp: str):
+    """(word-level Levenshtein distance, reference words) over space-split words, through the
+    same id-sequence edit distance as the CER."""
+    rw, hw = ref.split(), hyp.split()
+    ids = {}
+    a = [ids.setdefault(w, len(ids)) for w in rw]
+    b = [ids.setdefault(w, len(ids)) for w in hw]
+    return levenshtein(a, b), len(rw)
+
+
+def load_lm(args):
+    """The LM of --lm_path (None without one); it needs the beam decoder."""
+    path = getattr(args, "lm_path", "")
+    if not path:
+        return None
+    if args.decoder != "beam":
+        raise ValueError("--lm_path needs --decoder beam")
+    from .lm import CharNgramLM
+    return CharNgramLM.read(path)
+
+
+def decode(logits: torch.Tensor, lens: torch.Tensor, decoder: str, beam_width: int, lm=None,
+           lm_weight: float = 1.0, label_bonus: float = 0.0) -> List[List[int]]:
     from .ops import decode as D
     if decoder == "greedy":
         if logits.is_cuda:
@@ -68,18 +90,23 @@ def decode(logits: torch.Tensor, lens: torch.Tensor, decoder: str, beam_width: i
             return native.load().greedy_collapse(best, lens.cpu().numpy().astype(np.int32), BLANK)
         except RuntimeError:
             return R.greedy_decode(lp, lens)
-    return D.beam_decode(logits, lens, beam_width, BLANK, -10.0)
+    if lm is None:
+        return D.beam_decode(logits, lens, beam_width, BLANK, -10.0)
+    return D.beam_decode(logits, lens, beam_width, BLANK, -10.0, lm=lm, lm_weight=lm_weight, label_bonus=label_bonus)
 
 
-def eval_once(model, args, data, num_iter: int, display: bool) -> float:
+def eval_once(model, args, data, num_iter: int, display: bool, lm=None, wer_out=None) -> float:
+    """Mean CER in percent; with ``wer_out`` (a list) the corpus WER in percent is appended to it."""
     model.eval()
     cers = []
+    werr = wref = 0
     with torch.no_grad():
         for step in range(num_iter):
             hb = data.next()
             b = to_device(hb, model.fc_weight.device)
             logits, lens = model(b["feats"], b["seq_lens"])
-            preds = decode(logits, lens, args.decoder, args.beam_width)
+            preds = decode(logits, lens, args.decoder, args.beam_width, lm, getattr(args, "lm_weight", 1.0),
+                           getattr(args, "label_bonus", 0.0))
             if model.engine == "hip":
                 # decode() synchronised already: surface a recurrence timeout (undefined
                 # outputs) for this batch instead of reporting a CER computed from them
@@ -89,8 +116,13 @@ def eval_once(model, args, data, num_iter: int, display: bool) -> float:
                 lab = hb.labels[i, : hb.label_lens[i]].tolist()
                 ref_s, hyp_s = ids_to_text(lab), ids_to_text(p)
                 cers.append(levenshtein(ref_s, hyp_s) / max(1, len(ref_s)))
+                if wer_out is not None:
+                    e, n = word_errors(ref_s, hyp_s)
+                    werr, wref = werr + e, wref + n
                 if display and i < 2:
                     print(ref_s + " vs " + hyp_s)
+    if wer_out is not None:
+        wer_out.append(100.0 * werr / wref if wref else float("nan"))
     return float(np.mean(cers)) * 100.0 if cers else float("nan")
 
 
@@ -122,6 +154,7 @@ def main(argv=None) -> int:
     model = DeepSpeech2(**C.model_kwargs_from_args(args)).to(dev)
     model.set_engine(engine, dtype)
     data = build_eval_data(args)
+    lm = load_lm(args)
     n = args.num_examples or NUM_EXAMPLES.get(args.eval_data, 2048)
     num_iter = int(math.ceil(n / args.batch_size))
     events = EventWriter(args.eval_dir)
@@ -134,10 +167,16 @@ def main(argv=None) -> int:
             tensors = {k: v for k, v in CK.load_checkpoint_file(path).items() if isinstance(v, torch.Tensor)}
             CK.load_model_from_tf(model, tensors, strict=True, use_ema=args.use_ema)
             step = CK.step_from_path(path)
-            cer = eval_once(model, args, data, num_iter, args.display)
+            wer = [] if args.report_wer else None
+            cer = eval_once(model, args, data, num_iter, args.display, lm=lm, wer_out=wer)
             print("%s: char_err_rate = %.3f %%" % (datetime.now(), cer), flush=True)
-            events.scalars(step, {"char_err_rate": cer})
-            jl.write(step, char_err_rate=cer, checkpoint=os.path.basename(path))
+            if wer is None:
+                events.scalars(step, {"char_err_rate": cer})
+                jl.write(step, char_err_rate=cer, checkpoint=os.path.basename(path))
+            else:
+                print("%s: word_err_rate = %.3f %%" % (datetime.now(), wer[0]), flush=True)
+                events.scalars(step, {"char_err_rate": cer, "word_err_rate": wer[0]})
+                jl.write(step, char_err_rate=cer, word_err_rate=wer[0], checkpoint=os.path.basename(path))
         if args.run_once:
             break
         time.sleep(args.eval_interval_secs)

@@ -3,13 +3,14 @@
 beam-search decoder on one MI355X).
 
   python tools/bench_infer.py [--layers 5] [--hidden 800] [--seconds 20] [--chunks 0.25,0.5,1.0]
-                              [--batches 1,32] [--decoders greedy,beam] [--audio]
+                              [--batches 1,32] [--decoders greedy,beam] [--audio] [--lm ORDER]
 
 RTF = compute seconds / audio seconds per stream (B concurrent streams share each chunk
 launch, so B streams at RTF r serve B * (1 / r) x real time). Random-init weights and
 synthetic 161-bin features (no checkpoint or dataset offline). One JSON line per setting.
 ``--audio`` streams synthetic int16 PCM through StreamingRecognizer.accept_audio instead, so the
-RTF includes the featurization (csrc/featurize.hip).
+RTF includes the featurization (csrc/featurize.hip). ``--lm ORDER`` fuses a character n-gram LM
+of that order, trained on seeded synthetic text, into the beam decoder (deepspeech_amd/lm.py).
 """
 import argparse
 import json
@@ -36,7 +37,15 @@ def main():
     ap.add_argument("--beam_width", type=int, default=16)
     ap.add_argument("--engine", default="hip")
     ap.add_argument("--audio", action="store_true", help="stream int16 PCM (featurization included in the RTF)")
+    ap.add_argument("--lm", type=int, default=0, metavar="ORDER",
+                    help="beam decoder with a character LM of this order (seeded synthetic text)")
+    ap.add_argument("--lm_weight", type=float, default=0.8)
+    ap.add_argument("--label_bonus", type=float, default=0.5)
     a = ap.parse_args()
+    lm = None
+    if a.lm > 0:
+        from deepspeech_amd.lm import CharNgramLM, synthetic_corpus
+        lm = CharNgramLM.train(synthetic_corpus(2000, seed=0, vocab=400), a.lm)
     extra = {"audio": True} if a.audio else {}
     data = "synthetic int16 PCM, random-init weights" if a.audio else "synthetic features, random-init weights"
     dev = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -49,14 +58,18 @@ def main():
     for B in [int(x) for x in a.batches.split(",")]:
         for c in [float(x) for x in a.chunks.split(",")]:
             for d in a.decoders.split(","):
-                r, _ = rtf(m, seconds=a.seconds, chunk_s=c, batch=B, decoder=d, beam_width=a.beam_width,
-                           **extra)
+                kw = dict(extra)
+                if lm is not None and d == "beam":
+                    kw.update(lm=lm, lm_weight=a.lm_weight, label_bonus=a.label_bonus)
+                r, _ = rtf(m, seconds=a.seconds, chunk_s=c, batch=B, decoder=d, beam_width=a.beam_width, **kw)
                 print(json.dumps({"metric": "streaming RTF (lower is better)", "model": "DS2 2xconv(32) + %dx uni-%s-%d"
                                   % (a.layers, a.cell.upper(), a.hidden), "engine": eng, "streams": B,
                                   "chunk_s": c, "decoder": d, "beam_width": a.beam_width if d == "beam" else None,
                                   "rtf": round(r, 5), "x_realtime_per_stream": round(1.0 / r, 1) if r > 0 else None,
                                   "x_realtime_total": round(B / r, 1) if r > 0 else None,
-                                  "audio_s": a.seconds, "data": data}),
+                                  "audio_s": a.seconds, "data": data,
+                                  **({"lm_order": a.lm, "lm_states": int(lm.compile()[0].shape[0])}
+                                     if "lm" in kw else {})}),
                       flush=True)
 
 
