@@ -36,6 +36,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "rnn_exchange.h"
 
 using namespace ds2;
 
@@ -82,65 +83,6 @@ __device__ __forceinline__ void f8_presleep() {
   for (int i = 0; i < N; ++i) __builtin_amdgcn_s_sleep(1);
 }
 
-__device__ __forceinline__ unsigned xcc_id8() {
-  unsigned v;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-  return v & 0xf;
-}
-
-// group = blockIdx % 8 (<= 8 groups: one XCD each under round-robin dispatch), member =
-// blockIdx / 8; otherwise contiguous ranges
-__device__ __forceinline__ bool take_role8(int xcd_map, int ngroups, int P, int& grp, int& mem) {
-  if (xcd_map) {
-    const int slot = blockIdx.x & 7;
-    if (slot >= ngroups) return false;
-    grp = slot;
-    mem = blockIdx.x >> 3;
-  } else {
-    grp = blockIdx.x / P;
-    mem = blockIdx.x % P;
-  }
-  return mem < P;
-}
-
-// 1: every member on one XCD, 0: spread, -1: timeout (wave 0)
-__device__ int census8(unsigned* census, int grp, int mem, int P, long long timeout, unsigned* err) {
-  const int lane = threadIdx.x & 63;
-  unsigned* c = census + (size_t)grp * P;
-  if (lane == 0) __hip_atomic_store(c + mem, xcc_id8(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const long long t0 = __builtin_amdgcn_s_memrealtime();
-  while (true) {
-    bool ready = true, same = true;
-    unsigned first = 0xffffffffu;
-    for (int q = lane; q < P; q += 64) {
-      const unsigned v = __hip_atomic_load(c + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      ready = ready && (v != 0xffffffffu);
-      if (q == lane) first = v;
-      same = same && (v == first);
-    }
-    if (__all(ready)) {
-      const unsigned x0 = __shfl(first, 0, 64);
-      return __all(same && (lane >= P || first == x0)) ? 1 : 0;
-    }
-    if (__builtin_amdgcn_s_memrealtime() - t0 > timeout) {
-      if (lane == 0) atomicOr(err, 2u);
-      return -1;
-    }
-    __builtin_amdgcn_s_sleep(2);
-  }
-}
-
-// no byte of the granule is the sentinel 0xFF: SWAR "has a zero byte" on the complement
-__device__ __forceinline__ bool granule8_ready(i32x4 v) {
-  unsigned any = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const unsigned w = ~(unsigned)v[i];
-    any |= (w - 0x01010101u) & ~w & 0x80808080u;
-  }
-  return any == 0;
-}
-
 // f32 -> e4m3 byte (OCP, round to nearest even, saturating); a NaN becomes 0x7F, never the
 // sentinel 0xFF
 __device__ __forceinline__ unsigned f2e4m3(float x) {
@@ -164,7 +106,7 @@ __global__ __launch_bounds__(F8TH) void rnnf8_fwd_kernel(XF8 a) {
   extern __shared__ __attribute__((aligned(16))) i32x8 ul_dyn[];   // [KL][G8W][G3][64]
 
   int grp, mem;
-  if (!take_role8(a.xcd_map, a.ngroups, a.P, grp, mem)) return;
+  if (!take_role(a.xcd_map, a.ngroups, a.P, grp, mem)) return;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int H = a.H, N = a.N, NP = a.NP, R = a.R;
@@ -174,15 +116,13 @@ __global__ __launch_bounds__(F8TH) void rnnf8_fwd_kernel(XF8 a) {
   const int g16 = lane >> 4;                     // lane group: rows 4 g16 .. 4 g16 + 3 of the tile
   const int ec = 16 * uq + (lane & 15);          // this lane's unit within the workgroup
   const int erow0 = 4 * g16 + 2 * kh;            // its two cell elements: rows erow0, erow0 + 1
-  if (tid < ROWS8) len_s[tid] = (tid < R && r0 + tid < N) ? a.lens[r0 + tid] : 0;
-  if (wave == 0) {
-    const int m = census8(a.census, grp, mem, a.P, a.timeout, a.err);
-    if (lane == 0) { s_mode = m; s_abort = (m < 0); }
-  }
+  group_start(len_s, s_mode, s_abort, a, r0, R, N, grp, mem, a.P, wave);
   __syncthreads();
   if (s_abort) return;
 
-  // memory wave: gx granule q -> (row, gate, 8-unit chunk); R x 3 x 8 = 192 granules max
+  // memory wave: gx granule q -> (row, gate, 8-unit chunk); R x 3 x 8 = 192 granules max.
+  // Own load / put (64 units, 8 staged rows, an element-wise bf16 ring; three ring slots in
+  // rnnf8h_fwd_kernel) and own store (hx as bf16x8, no fused sum); the schedule is the shared one
   constexpr int RGL = (ROWS8 * G3 * (UPW8 / 8) + 63) / 64;     // 3
   i32x4 gpre[RGL];
   const int NRG = R * G3 * (UPW8 / 8);
@@ -211,6 +151,7 @@ __global__ __launch_bounds__(F8TH) void rnnf8_fwd_kernel(XF8 a) {
       }
     }
   };
+  auto no_ysum = [](int) {};   // these kernels write per-direction outputs: no fused sum to load ahead
   // outputs of step s: lane -> (row = lane / 8, 8 units (lane % 8) * 8)
   auto mw_store = [&](int s) {
     const int row = lane >> 3, c8 = (lane & 7) * 8;
@@ -249,11 +190,7 @@ __global__ __launch_bounds__(F8TH) void rnnf8_fwd_kernel(XF8 a) {
       *reinterpret_cast<bf16x8*>(a.y[dir] + ((size_t)t * N + b) * H + u) = yb;
     }
   };
-  if (wave == MEMW8) {
-    mw_load(0);
-    mw_put(0);
-    if (a.steps > 1) mw_load(1);
-  }
+  if (wave == MEMW8) mw_prologue(a.steps, mw_load, mw_put);
   __syncthreads();                                   // gx ring slot 0
   const bool plain = s_mode == 1;
   const unsigned hq_bytes = (unsigned)((size_t)(a.steps + 1) * NP * H);
@@ -384,18 +321,13 @@ __global__ __launch_bounds__(F8TH) void rnnf8_fwd_kernel(XF8 a) {
     }
   } else {
     for (int s = 0; s < a.steps; ++s) {
-      if (s + 1 < a.steps) mw_put(s + 1);
-      if (s >= 2) mw_store(s - 2);
-      if (s + 2 < a.steps) mw_load(s + 2);
+      mw_step(s, a.steps, false, no_ysum, mw_put, mw_store, mw_load);
       lds_barrier();
       if (s_abort) break;
     }
   }
   __syncthreads();
-  if (wave == MEMW8 && !s_abort) {
-    if (a.steps >= 2) mw_store(a.steps - 2);
-    if (a.steps >= 1) mw_store(a.steps - 1);
-  }
+  if (wave == MEMW8 && !s_abort) mw_drain(a.steps, false, no_ysum, mw_store);
 }
 
 // Generation 2 of the fp8 forward (rnnf8h_fwd_kernel): 8 MFMA waves = 2 unit halves (uh =
@@ -427,7 +359,7 @@ __global__ __launch_bounds__(F8TH) void rnnf8h_fwd_kernel(XF8 a) {
   __shared__ i32x8 ul_s[NLW > 0 ? 2 * NLW : 1][NT][64];   // [uh + 2 kq][tile][lane], kq < NLW
 
   int grp, mem;
-  if (!take_role8(a.xcd_map, a.ngroups, a.P, grp, mem)) return;
+  if (!take_role(a.xcd_map, a.ngroups, a.P, grp, mem)) return;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int H = a.H, N = a.N, NP = a.NP, R = a.R;
@@ -437,16 +369,15 @@ __global__ __launch_bounds__(F8TH) void rnnf8h_fwd_kernel(XF8 a) {
   const int g16 = lane >> 4;
   const int erow = 4 * g16 + kq;                 // this lane's cell row (element j = kq)
   const int er = min(erow, ROWS8 - 1);           // for LDS reads (rows >= R are not real)
-  if (tid < ROWS8) len_s[tid] = (tid < R && r0 + tid < N) ? a.lens[r0 + tid] : 0;
+  group_lens(len_s, a, r0, R, N);
   if (tid < G3 * UPW8) bh_s[tid / UPW8][tid % UPW8] = a.bh[dir] ? a.bh[dir][(tid / UPW8) * H + u0 + tid % UPW8] : 0.f;
-  if (wave == 0) {
-    const int m = census8(a.census, grp, mem, a.P, a.timeout, a.err);
-    if (lane == 0) { s_mode = m; s_abort = (m < 0); }
-  }
+  group_mode(s_mode, s_abort, a, grp, mem, a.P, wave);
   __syncthreads();
   if (s_abort) return;
 
-  // memory wave: gx granule q -> (row, gate, 8-unit chunk); R x 3 x 8 = 192 granules max
+  // memory wave: gx granule q -> (row, gate, 8-unit chunk); R x 3 x 8 = 192 granules max.
+  // Own load / put (64 units, 8 staged rows, an element-wise bf16 ring; three ring slots in
+  // rnnf8h_fwd_kernel) and own store (hx as bf16x8, no fused sum); the schedule is the shared one
   constexpr int RGL = (ROWS8 * G3 * (UPW8 / 8) + 63) / 64;     // 3
   i32x4 gpre[RGL];
   const int NRG = R * G3 * (UPW8 / 8);
@@ -475,6 +406,7 @@ __global__ __launch_bounds__(F8TH) void rnnf8h_fwd_kernel(XF8 a) {
       }
     }
   };
+  auto no_ysum = [](int) {};   // these kernels write per-direction outputs: no fused sum to load ahead
   // outputs of step s: lane -> (row = lane / 8, 8 units (lane % 8) * 8)
   auto mw_store = [&](int s) {
     const int row = lane >> 3, c8 = (lane & 7) * 8;
@@ -513,11 +445,7 @@ __global__ __launch_bounds__(F8TH) void rnnf8h_fwd_kernel(XF8 a) {
       *reinterpret_cast<bf16x8*>(a.y[dir] + ((size_t)t * N + b) * H + u) = yb;
     }
   };
-  if (wave == MEMW8) {
-    mw_load(0);
-    mw_put(0);
-    if (a.steps > 1) mw_load(1);
-  }
+  if (wave == MEMW8) mw_prologue(a.steps, mw_load, mw_put);
   __syncthreads();                                   // gx ring slot 0
   const bool plain = s_mode == 1;
   const unsigned hq_bytes = (unsigned)((size_t)(a.steps + 1) * NP * H);
@@ -661,18 +589,13 @@ __global__ __launch_bounds__(F8TH) void rnnf8h_fwd_kernel(XF8 a) {
     }
   } else {
     for (int s = 0; s < a.steps; ++s) {
-      if (s + 1 < a.steps) mw_put(s + 1);
-      if (s >= 2) mw_store(s - 2);
-      if (s + 2 < a.steps) mw_load(s + 2);
+      mw_step(s, a.steps, false, no_ysum, mw_put, mw_store, mw_load);
       lds_barrier();
       if (s_abort) break;
     }
   }
   __syncthreads();
-  if (wave == MEMW8 && !s_abort) {
-    if (a.steps >= 2) mw_store(a.steps - 2);
-    if (a.steps >= 1) mw_store(a.steps - 1);
-  }
+  if (wave == MEMW8 && !s_abort) mw_drain(a.steps, false, no_ysum, mw_store);
 }
 
 // ------------------------------------------------------------------------------------
@@ -757,19 +680,16 @@ __global__ __launch_bounds__(BTH8) void rnnf8_bwd_kernel(XF8B a) {
   __shared__ int s_mode, s_abort;
 
   int grp, mem;
-  if (!take_role8(a.xcd_map, a.ngroups, a.P, grp, mem)) return;
+  if (!take_role(a.xcd_map, a.ngroups, a.P, grp, mem)) return;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int H = a.H, GH = G3 * H, N = a.N, NP = a.NP, R = a.R, P = a.P, MTS = H / 16, NPR = MTS / 2;
   const int bg = grp % a.BG, dir = grp / a.BG;
   const int r0 = bg * R, u0 = mem * UPW8;
-  if (tid < ROWS8) len_s[tid] = (tid < R && r0 + tid < N) ? a.lens[r0 + tid] : 0;
+  group_lens(len_s, a, r0, R, N);
   if (tid < ROWS * 4) (&dsc_s[0][0])[tid] = 0x7f7f7f7f;
   for (int i = tid; i < 2 * ROWS * 128 / 4; i += BTH8) reinterpret_cast<int*>(&dq_s[0][0][0])[i] = 0;
-  if (wave == 0) {
-    const int m = census8(a.census, grp, mem, P, a.timeout, a.err);
-    if (lane == 0) { s_mode = m; s_abort = (m < 0); }
-  }
+  group_mode(s_mode, s_abort, a, grp, mem, P, wave);
   // resident A fragments of m-tile mt = 2 (wave + 7 (i >> 1)) + (i & 1): A[m][k] = U^T, unit m =
   // 16 mt + lane % 16, k-step 0: k in [16 g, +16) = gate 0 units u0 + 16 g.., [64 + 16 g, +16) =
   // gate 1; k-step 1: [16 g, +16) = gate 2 (the rest zero), g = lane / 16
@@ -863,12 +783,7 @@ __global__ __launch_bounds__(BTH8) void rnnf8_bwd_kernel(XF8B a) {
   const bool plain = s_mode == 1;
   const unsigned ring_bytes = (unsigned)((size_t)3 * a.BG * P * NPR * R * 64);
   const __amdgpu_buffer_rsrc_t rs_ring = make_rsrc(a.ring[dir], ring_bytes);
-  auto tag_of = [&](int s) -> unsigned { return (unsigned)(((a.steps - 1 - s) / 3) & 1); };
-  // [slot][bg][producer][unit pair][row][granule g][8 bf16]: granule (row, g) of pair p holds
-  // units 32 p + {4 g .. 4 g + 3, 16 + 4 g .. 16 + 4 g + 3}
-  auto ring_off16 = [&](int slot, int j, int pr, int row, int g) -> unsigned {
-    return (unsigned)((((((size_t)slot * a.BG + bg) * P + j) * NPR + pr) * R + row) * 4 + g) * 16u;
-  };
+  // use tag of P(s) and the bf16 ring layout: ring_tag / ring_off16 (rnn_exchange.h)
 
   if (wave < BMW8) {
     const int sa = __builtin_amdgcn_readfirstlane(a.uexp[dir]);
@@ -887,7 +802,7 @@ __global__ __launch_bounds__(BTH8) void rnnf8_bwd_kernel(XF8B a) {
           for (int q = 0; q < 8; ++q) acc8[pp][q] = 0.f;
         if (has_next && grow < R) {
           const int cs = (s + 1) % 3;
-          const unsigned want = tag_of(s + 1);
+          const unsigned want = ring_tag(a.steps, s + 1);
           unsigned off[2][NI];
           i32x4 v[2][NI];
 #pragma unroll
@@ -895,7 +810,7 @@ __global__ __launch_bounds__(BTH8) void rnnf8_bwd_kernel(XF8B a) {
 #pragma unroll
             for (int i = 0; i < NI; ++i) {
               const int j = min(wave + BMW8 * (2 * i + h), P - 1);
-              off[pp][i] = ring_off16(cs, j, 2 * mem + pp, grow, gg);
+              off[pp][i] = ring_off16(a.BG, bg, P, NPR, R, cs, j, 2 * mem + pp, grow, gg);
               v[pp][i] = load_sc1_b128(rs_ring, off[pp][i]);
             }
           const long long t0 = __builtin_amdgcn_s_memrealtime();
@@ -989,7 +904,7 @@ __global__ __launch_bounds__(BTH8) void rnnf8_bwd_kernel(XF8B a) {
       // (M) publish P(s) = dg_s[:, own cols] . U[own cols, :] into ring slot s % 3
       if (s > 0) {
         const int ws = s % 3;
-        const unsigned tagmask = tag_of(s) ? 0x00010001u : 0u;
+        const unsigned tagmask = ring_tag(a.steps, s) ? 0x00010001u : 0u;
         const bool prow = (lane & 15) < R;
         const unsigned char* dr = &dq_s[0][lane & 15][16 * (lane >> 4)];
         const i32x8 b0 = __builtin_shufflevector(*reinterpret_cast<const i32x4*>(dr),
@@ -1001,7 +916,8 @@ __global__ __launch_bounds__(BTH8) void rnnf8_bwd_kernel(XF8B a) {
         constexpr int NPW = MTU / 2;
         unsigned offp[NPW];
 #pragma unroll
-        for (int k = 0; k < NPW; ++k) offp[k] = ring_off16(ws, mem, min(wave + BMW8 * k, NPR - 1), lane & 15, lane >> 4);
+        for (int k = 0; k < NPW; ++k)
+          offp[k] = ring_off16(a.BG, bg, P, NPR, R, ws, mem, min(wave + BMW8 * k, NPR - 1), lane & 15, lane >> 4);
         auto publish = [&](auto PLAIN) {
 #pragma unroll
           for (int k = 0; k < NPW; ++k) {
@@ -1017,12 +933,8 @@ __global__ __launch_bounds__(BTH8) void rnnf8_bwd_kernel(XF8B a) {
             // publish then stored partly-updated sums: tools/probe_mfma_layout.hip and the
             // emulation test). The operand-tied s_nop keeps 8 more between them.
             asm volatile("s_nop 7" : "+v"(a0), "+v"(a1));
-            if (prow && wave + BMW8 * k < NPR) {
-              const i32x4 v = {(int)bf16x2_tagged(a0[0], a0[1], tagmask), (int)bf16x2_tagged(a0[2], a0[3], tagmask),
-                               (int)bf16x2_tagged(a1[0], a1[1], tagmask), (int)bf16x2_tagged(a1[2], a1[3], tagmask)};
-              if constexpr (decltype(PLAIN)::value) store_b128(rs_ring, offp[k], v);
-              else store_sc1_b128(rs_ring, offp[k], v);
-            }
+            if (prow && wave + BMW8 * k < NPR)
+              publish_pair<decltype(PLAIN)::value>(rs_ring, offp[k], a0, a1, tagmask);
           }
         };
         if (plain) publish(std::true_type{});

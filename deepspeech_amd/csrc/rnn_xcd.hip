@@ -5,7 +5,9 @@
 //   rnne_fwd_kernel   generation 5 GRU forward (H <= 1024): 8 K-eighths, one poller per granule
 //   rnnrs_bwd_kernel  generation 3 BPTT: reduce-scatter of tagged-bf16 partials
 //   rnnw_fwd_kernel / rnnw_bwd_kernel   64-unit one-gate layers wider than an XCD (ReLU-1760)
-// The notes below describe the shared exchange protocol (introduced with generation 2).
+// The notes below describe the shared exchange protocol (introduced with generation 2); its
+// device primitives (census, sentinel / tag tests, granule stores, fused direction sum, ring
+// addressing, stamps) are defined once in rnn_exchange.h, for this file and rnn_fp8.hip.
 //
 // Reference behaviour: src/custom_ops.py:36-96 (CustomRNNCell2 + stacked_brnn through
 // tf.nn.bidirectional_dynamic_rnn: outputs zero past each length, the backward direction
@@ -41,6 +43,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "rnn_exchange.h"
 
 using namespace ds2;
 
@@ -70,114 +73,10 @@ struct XFwd {
   unsigned long long* stamps;   // optional [grid][8] phase cycle sums (diagnostics)
 };
 
-// Phase stamps (diagnostics; a null stamps pointer costs one uniform branch per phase).
-struct Stamps {
-  unsigned long long acc[6] = {0, 0, 0, 0, 0, 0};
-  unsigned long long prev = 0;
-  bool on;
-  __device__ explicit Stamps(bool o) : on(o) {}
-  __device__ __forceinline__ void mark(int i) {
-    if (!on) return;
-    unsigned long long t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    if (prev && i >= 0) acc[i] += t - prev;
-    prev = t;
-  }
-  __device__ __forceinline__ void store(unsigned long long* dst, int base) {
-    if (!on) return;
-    for (int k = 0; k < 6; ++k) dst[(size_t)blockIdx.x * 8 + base + k] = acc[k];
-  }
-};
-
-// compile-time-off variant: the stamp accumulators would otherwise hold ~14 VGPRs of every
-// wave for the whole launch (enough to push a 3-waves-per-SIMD kernel into spilling)
-struct NoStamps {
-  unsigned long long acc[6];
-  bool on = false;
-  __device__ explicit NoStamps(bool) {}
-  __device__ __forceinline__ void mark(int) {}
-  __device__ __forceinline__ void store(unsigned long long*, int) {}
-};
-
-__device__ __forceinline__ unsigned xcc_id() {
-  unsigned v;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-  return v & 0xf;
-}
-
 // bf16 rounding that never produces the sentinel 0xFFFF (any NaN -> canonical 0x7FC0)
 __device__ __forceinline__ bf16_t f2bf_x(float f) {
   const bf16_t b = f2bf(f);
   return ((b & 0x7f80u) == 0x7f80u && (b & 0x7fu)) ? (bf16_t)0x7fc0 : b;
-}
-
-// no 16-bit half of the granule is the sentinel 0xFFFF: SWAR "has a zero half" test on the
-// complement, (~w - 0x00010001) & w & 0x80008000 (a few VALU ops per dword; this check runs
-// on every poll of the latency-critical exchange)
-__device__ __forceinline__ bool granule_ready(i32x4 v) {
-  unsigned any = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const unsigned w = (unsigned)v[i];
-    any |= (~w - 0x00010001u) & w & 0x80008000u;
-  }
-  return any == 0;
-}
-
-__device__ __forceinline__ void store_granule(bool plain, __amdgpu_buffer_rsrc_t rs, bf16_t* base, unsigned off,
-                                              i32x4 v) {
-  (void)base;
-  if (plain) {
-    store_b128(rs, off, v);
-  } else {
-    store_sc1_b128(rs, off, v);
-  }
-}
-
-// Group role. xcd_map (host-chosen: <= 8 groups of <= CUs/8 members): group =
-// blockIdx % 8, so under round-robin dispatch a group shares one XCD; otherwise groups
-// are contiguous block ranges. Returns false for surplus blocks (no role).
-__device__ __forceinline__ bool take_role(int xcd_map, int ngroups, int P, int& grp, int& mem) {
-  if (xcd_map) {
-    const int slot = blockIdx.x & 7;
-    if (slot >= ngroups) return false;
-    grp = slot;
-    mem = blockIdx.x >> 3;
-  } else {
-    grp = blockIdx.x / P;
-    mem = blockIdx.x % P;
-  }
-  return mem < P;
-}
-
-// Every member of the group publishes its XCC id; the group is "local" iff all agree.
-// Runs on wave 0; returns 1 (local), 0 (spread) or -1 (timeout).
-__device__ int group_census(unsigned* census, int grp, int mem, int P, long long timeout, unsigned* err) {
-  const int lane = threadIdx.x & 63;
-  unsigned* c = census + (size_t)grp * P;
-  if (lane == 0) __hip_atomic_store(c + mem, xcc_id(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const long long t0 = __builtin_amdgcn_s_memrealtime();
-  while (true) {
-    bool ready = true;
-    unsigned first = 0xffffffffu;
-    bool same = true;
-    for (int q = lane; q < P; q += 64) {
-      const unsigned v = __hip_atomic_load(c + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      ready = ready && (v != 0xffffffffu);
-      if (q == lane) first = v;
-      same = same && (v == first);
-    }
-    if (__all(ready)) {
-      const unsigned x0 = __shfl(first, 0, 64);
-      const bool all_same = __all(same && (lane >= P || first == x0));
-      return all_same ? 1 : 0;
-    }
-    if (__builtin_amdgcn_s_memrealtime() - t0 > timeout) {
-      if (lane == 0) atomicOr(err, 2u);
-      return -1;
-    }
-    __builtin_amdgcn_s_sleep(2);
-  }
 }
 
 // ------------------------------------------------------------------------------------
@@ -236,17 +135,6 @@ __device__ __forceinline__ bool poll_mfma(__amdgpu_buffer_rsrc_t rs, const unsig
 // late. (poll_mfma reloads only the granule it is waiting on, so k-steps whose first load
 // came back early-stale cost one serial round trip each.) The MFMAs still run in k order,
 // so the accumulation order — and the result — is deterministic.
-// Explicit vmcnt(0) at the poll's exits. Every load of the poll has been waited for there
-// already (the last check consumed it), but the CFG also has an edge from a re-issue to the
-// exit, so the waitcnt pass assumed loads in flight and put a vmcnt(0) at the head of the
-// NEXT step — behind the step's own h store, whose write acknowledgement then delayed the
-// next step's first poll by an L2 round trip. A counted wait here costs nothing (nothing is
-// in flight) and tells the pass so.
-__device__ __forceinline__ void drain_vm() {
-#ifndef DS2_NO_DRAIN          // A/B: build.py --variant nodrain -D DS2_NO_DRAIN
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-#endif
-}
 
 template <int KB, typename MfmaFn>
 __device__ __forceinline__ bool poll_mfma_par(__amdgpu_buffer_rsrc_t rs, const unsigned (&off)[KB],
@@ -309,14 +197,10 @@ __global__ __launch_bounds__(NTH) void rnnx_fwd_kernel(XFwd a) {
   const int H = a.H, KS = H / 32, N = a.N, NP = a.NP, R = a.R;
   const int bg = grp % a.BG, dir = grp / a.BG;
   const int r0 = bg * R, u0 = mem * UPW;
-  if (tid < ROWS) len_s[tid] = (tid < R && r0 + tid < N) ? a.lens[r0 + tid] : 0;
+  group_lens(len_s, a, r0, R, N);
   if (tid < G * UPW)
     bh_s[tid / UPW][tid % UPW] = (CELL == CELL_GRU && a.bh[dir]) ? a.bh[dir][(tid / UPW) * H + u0 + tid % UPW] : 0.f;
-  if (wave == 0) {
-    int m = group_census(a.census, grp, mem, a.P, a.timeout, a.err);
-    if ((a.knobs & 32768) && m > 0) m = 0;      // knob 32768: force write-through (timing)
-    if (lane == 0) { s_mode = m; s_abort = (m < 0); }
-  }
+  group_mode<32768>(s_mode, s_abort, a, grp, mem, a.P, wave);   // knob 32768: write-through
 
   // resident U fragments of the MFMA waves: B[k][c] = U[g*H + u0 + 16*half + c][k]
   bf16x8 uf[KB][NTL];
@@ -502,7 +386,7 @@ __global__ __launch_bounds__(NTH) void rnnx_fwd_kernel(XFwd a) {
           if ((c & 7) == 0 && row < R) {
             const i32x4 v = {(int)pr, q1, q2, q3};
             const unsigned off = (unsigned)((((size_t)(s + 1) * NP + r0 + row) * H + u0 + c) * 2);
-            store_granule(plain, rs_hx, hxd, off, v);
+            store_granule(plain, rs_hx, off, v);
           }
         }
       }
@@ -527,8 +411,7 @@ __global__ __launch_bounds__(NTH) void rnnx_fwd_kernel(XFwd a) {
     if (a.steps >= 2) mw_store(a.steps - 2);
     if (a.steps >= 1) mw_store(a.steps - 1);
   }
-  if (wave == 0) { st.acc[5] = (unsigned long long)(s_mode + 10); st.store(a.stamps, 0); }
-  if (wave == MEMW && st.on) { a.stamps[(size_t)blockIdx.x * 8 + 6] = st.acc[0]; a.stamps[(size_t)blockIdx.x * 8 + 7] = st.acc[1]; }
+  stamp_flush(st, a.stamps, wave, 0, MEMW, s_mode);
 }
 
 // ------------------------------------------------------------------------------------
@@ -595,6 +478,8 @@ __global__ __launch_bounds__(QTH) void rnnq_fwd_kernel(XFwd a) {
   // 10 % slower: the early pollers' retry loads compete with the epilogue.)
   const int erow = 4 * (lane >> 4) + (kq & 3);    // this lane's cell element (MFMA waves)
   const int ec = 16 * uh + (lane & 15);
+  // group_start, inline: through the helper the ReLU instantiations KB 4..8 gain 4 VGPRs
+  // (KB = 5 drops from 7 to 6 waves per SIMD)
   if (tid < ROWS) len_s[tid] = (tid < R && r0 + tid < N) ? a.lens[r0 + tid] : 0;
   if (wave == 0) {
     int m = group_census(a.census, grp, mem, a.P, a.timeout, a.err);
@@ -605,7 +490,10 @@ __global__ __launch_bounds__(QTH) void rnnq_fwd_kernel(XFwd a) {
   __syncthreads();   // len_s / census
   if (s_abort) return;
 
-  // memory wave: gx granule q -> (row, gate, 8-unit chunk)
+  // memory wave: gx granule q -> (row, gate, 8-unit chunk). The bodies below are the same in
+  // rnnq_fwd_kernel and rnne_fwd_kernel but for the ring's element type; as shared function
+  // templates or one struct they cost VGPRs, scratch or occupancy in both (the profile), so only
+  // the step schedule (mw_prologue / mw_step / mw_drain) and dirsum_store are shared
   i32x4 gpre[RGL];
   const int NRG = R * G * (UPW / 8);
   auto mw_load = [&](int s) {
@@ -688,52 +576,17 @@ __global__ __launch_bounds__(QTH) void rnnq_fwd_kernel(XFwd a) {
           if (a.ysum == nullptr) {
             *reinterpret_cast<uint2*>(a.y[dir] + ((size_t)t * N + b) * H + u) = o;
           } else {
-            // Fused direction sum (reference: the fw + bw outputs summed by the caller,
-            // src/custom_ops.py:36-96). Position t is produced by the forward direction at
-            // step t and by the backward one at step L-1-t (padding positions: both at step
-            // t). The direction that produces it LATER (ties: the backward one) waits for the
-            // other's bf16 value in the sentinel-filled sum buffer and writes the bf16 sum,
-            // rounding exactly like bf16 + bf16 in torch; the earlier one writes its value
-            // through (sc1: the other direction's groups live on other XCDs). No cycle: the
-            // later side of a pair only waits for a step the earlier side reached first.
+            // fused direction sum: dirsum_store (rnn_exchange.h)
             unsigned long long* p = ysum_ptr(s, j);
             const int other = (s < L) ? (L - 1 - s) : s;
             const bool later = s > other || (s == other && dir == 1);
-            auto canon = [](unsigned h) { return (h & 0xffffu) == 0xffffu ? 0x7fc0u : (h & 0xffffu); };
-            if (!later) {
-              o.x = canon(o.x) | (canon(o.x >> 16) << 16);
-              o.y = canon(o.y) | (canon(o.y >> 16) << 16);
-              __hip_atomic_store(p, ((unsigned long long)o.y << 32) | o.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-              const long long t0 = __builtin_amdgcn_s_memrealtime();
-              unsigned long long q = yq[j];           // usually already there (loaded ahead)
-              while (true) {
-                const unsigned w0 = (unsigned)q, w1 = (unsigned)(q >> 32);
-                const bool ready = ((~w0 - 0x00010001u) & w0 & 0x80008000u) == 0 &&
-                                   ((~w1 - 0x00010001u) & w1 & 0x80008000u) == 0;
-                if (ready) break;
-                if (__builtin_amdgcn_s_memrealtime() - t0 > a.timeout) { atomicOr(a.err, 4u); break; }
-                __builtin_amdgcn_s_sleep(2);
-                q = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              }
-              const unsigned q0 = (unsigned)q, q1 = (unsigned)(q >> 32);
-              auto add2 = [](unsigned x, unsigned y) {      // two bf16 pairs -> rounded bf16 sums
-                const unsigned lo = f2bf(__uint_as_float(x << 16) + __uint_as_float(y << 16));
-                const unsigned hi = f2bf(__uint_as_float(x & 0xffff0000u) + __uint_as_float(y & 0xffff0000u));
-                return lo | (hi << 16);
-              };
-              *reinterpret_cast<uint2*>(p) = make_uint2(add2(o.x, q0), add2(o.y, q1));
-            }
+            dirsum_store(p, o, yq[j], later, a);
           }
         }
       }
     }
   };
-  if (wave == QW) {
-    mw_load(0);
-    mw_put(0);
-    if (a.steps > 1) mw_load(1);
-  }
+  if (wave == QW) mw_prologue(a.steps, mw_load, mw_put);
   __syncthreads();   // gx ring slot 0
   const bool plain = s_mode == 1;
   const unsigned hx_bytes = (unsigned)((size_t)(a.steps + 1) * NP * H * 2);
@@ -850,18 +703,10 @@ __global__ __launch_bounds__(QTH) void rnnq_fwd_kernel(XFwd a) {
       }
       const float hnew = act ? hn : hreg;
       hreg = hnew;
-      // hardware RNE conversion; 0xFFFF (the sentinel, a negative NaN) -> canonical NaN
-      unsigned hq = (unsigned)__builtin_bit_cast(unsigned short, (__bf16)hnew);
-      hq = hq == 0xffffu ? 0x7fc0u : hq;
-      // 16-B exchange granule = 8 consecutive units of one row = 8 consecutive lanes
-      const unsigned pr = hq | ((unsigned)__builtin_amdgcn_update_dpp(0, (int)hq, 0x101, 0xf, 0xf, false) << 16);
-      const int q1 = __builtin_amdgcn_update_dpp(0, (int)pr, 0x102, 0xf, 0xf, false);
-      const int q2 = __builtin_amdgcn_update_dpp(0, (int)pr, 0x104, 0xf, 0xf, false);
-      const int q3 = __builtin_amdgcn_update_dpp(0, (int)pr, 0x106, 0xf, 0xf, false);
+      const i32x4 v = pack_h(hnew);
       if ((lane & 7) == 0 && erow_ok) {
-        const i32x4 v = {(int)pr, q1, q2, q3};
         const unsigned off = (unsigned)((((size_t)(s + 1) * NP + r0 + erow) * H + u0 + ec) * 2);
-        store_granule(plain, rs_hx, hxd, off, v);
+        store_granule(plain, rs_hx, off, v);
       }
       oh_s[s & 1][erow][ec] = hnew;
       oy_s[s & 1][erow][ec] = act ? hn : 0.f;
@@ -871,10 +716,7 @@ __global__ __launch_bounds__(QTH) void rnnq_fwd_kernel(XFwd a) {
   } else {
     for (int s = 0; s < a.steps; ++s) {
       st.mark(-1);
-      if (a.ysum != nullptr && s >= 2) mw_ysum_load(s - 2);
-      if (s + 1 < a.steps) mw_put(s + 1);
-      if (s >= 2) mw_store(s - 2);
-      if (s + 2 < a.steps) mw_load(s + 2);
+      mw_step(s, a.steps, a.ysum != nullptr, mw_ysum_load, mw_put, mw_store, mw_load);
       st.mark(0);
       lds_barrier();
       st.mark(1);
@@ -882,18 +724,8 @@ __global__ __launch_bounds__(QTH) void rnnq_fwd_kernel(XFwd a) {
     }
   }
   __syncthreads();
-  if (wave == QW && !s_abort) {
-    if (a.steps >= 2) {
-      if (a.ysum != nullptr) mw_ysum_load(a.steps - 2);
-      mw_store(a.steps - 2);
-    }
-    if (a.steps >= 1) {
-      if (a.ysum != nullptr) mw_ysum_load(a.steps - 1);
-      mw_store(a.steps - 1);
-    }
-  }
-  if (STAMPS && wave == 0) { st.acc[5] = (unsigned long long)(s_mode + 10); st.store(a.stamps, 0); }
-  if (STAMPS && wave == QW && st.on) { a.stamps[(size_t)blockIdx.x * 8 + 6] = st.acc[0]; a.stamps[(size_t)blockIdx.x * 8 + 7] = st.acc[1]; }
+  if (wave == QW && !s_abort) mw_drain(a.steps, a.ysum != nullptr, mw_ysum_load, mw_store);
+  stamp_flush(st, a.stamps, wave, 0, QW, s_mode);
 }
 
 // ------------------------------------------------------------------------------------
@@ -943,16 +775,14 @@ __global__ __launch_bounds__(QTH) void rnne_fwd_kernel(XFwd a) {
   const int ke = (wave + 1) & 7;
   const int erow = 4 * (lane >> 4) + jo;
   const int ec = 16 * uh + (lane & 15);
-  if (tid < ROWS) len_s[tid] = (tid < R && r0 + tid < N) ? a.lens[r0 + tid] : 0;
-  if (wave == 0) {
-    int m = group_census(a.census, grp, mem, a.P, a.timeout, a.err);
-    if ((a.knobs & 32768) && m > 0) m = 0;      // knob 32768: force write-through (timing)
-    if (lane == 0) { s_mode = m; s_abort = (m < 0); }
-  }
+  group_start<32768>(len_s, s_mode, s_abort, a, r0, R, N, grp, mem, a.P, wave);   // knob 32768: write-through
   __syncthreads();
   if (s_abort) return;
 
-  // memory wave: gx granule q -> (row, gate, 8-unit chunk)
+  // memory wave: gx granule q -> (row, gate, 8-unit chunk). The bodies below are the same in
+  // rnnq_fwd_kernel and rnne_fwd_kernel but for the ring's element type; as shared function
+  // templates or one struct they cost VGPRs, scratch or occupancy in both (the profile), so only
+  // the step schedule (mw_prologue / mw_step / mw_drain) and dirsum_store are shared
   i32x4 gpre[RGL];
   const int NRG = R * G * (UPW / 8);
   auto mw_load = [&](int s) {
@@ -1034,52 +864,17 @@ __global__ __launch_bounds__(QTH) void rnne_fwd_kernel(XFwd a) {
           if (a.ysum == nullptr) {
             *reinterpret_cast<uint2*>(a.y[dir] + ((size_t)t * N + b) * H + u) = o;
           } else {
-            // Fused direction sum (reference: the fw + bw outputs summed by the caller,
-            // src/custom_ops.py:36-96). Position t is produced by the forward direction at
-            // step t and by the backward one at step L-1-t (padding positions: both at step
-            // t). The direction that produces it LATER (ties: the backward one) waits for the
-            // other's bf16 value in the sentinel-filled sum buffer and writes the bf16 sum,
-            // rounding exactly like bf16 + bf16 in torch; the earlier one writes its value
-            // through (sc1: the other direction's groups live on other XCDs). No cycle: the
-            // later side of a pair only waits for a step the earlier side reached first.
+            // fused direction sum: dirsum_store (rnn_exchange.h)
             unsigned long long* p = ysum_ptr(s, j);
             const int other = (s < L) ? (L - 1 - s) : s;
             const bool later = s > other || (s == other && dir == 1);
-            auto canon = [](unsigned h) { return (h & 0xffffu) == 0xffffu ? 0x7fc0u : (h & 0xffffu); };
-            if (!later) {
-              o.x = canon(o.x) | (canon(o.x >> 16) << 16);
-              o.y = canon(o.y) | (canon(o.y >> 16) << 16);
-              __hip_atomic_store(p, ((unsigned long long)o.y << 32) | o.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-              const long long t0 = __builtin_amdgcn_s_memrealtime();
-              unsigned long long q = yq[j];           // usually already there (loaded ahead)
-              while (true) {
-                const unsigned w0 = (unsigned)q, w1 = (unsigned)(q >> 32);
-                const bool ready = ((~w0 - 0x00010001u) & w0 & 0x80008000u) == 0 &&
-                                   ((~w1 - 0x00010001u) & w1 & 0x80008000u) == 0;
-                if (ready) break;
-                if (__builtin_amdgcn_s_memrealtime() - t0 > a.timeout) { atomicOr(a.err, 4u); break; }
-                __builtin_amdgcn_s_sleep(2);
-                q = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              }
-              const unsigned q0 = (unsigned)q, q1 = (unsigned)(q >> 32);
-              auto add2 = [](unsigned x, unsigned y) {      // two bf16 pairs -> rounded bf16 sums
-                const unsigned lo = f2bf(__uint_as_float(x << 16) + __uint_as_float(y << 16));
-                const unsigned hi = f2bf(__uint_as_float(x & 0xffff0000u) + __uint_as_float(y & 0xffff0000u));
-                return lo | (hi << 16);
-              };
-              *reinterpret_cast<uint2*>(p) = make_uint2(add2(o.x, q0), add2(o.y, q1));
-            }
+            dirsum_store(p, o, yq[j], later, a);
           }
         }
       }
     }
   };
-  if (wave == QW) {
-    mw_load(0);
-    mw_put(0);
-    if (a.steps > 1) mw_load(1);
-  }
+  if (wave == QW) mw_prologue(a.steps, mw_load, mw_put);
   __syncthreads();   // gx ring slot 0
   const bool plain = s_mode == 1;
   const unsigned hx_bytes = (unsigned)((size_t)(a.steps + 1) * NP * H * 2);
@@ -1179,17 +974,11 @@ __global__ __launch_bounds__(QTH) void rnne_fwd_kernel(XFwd a) {
       if (act) gsv = make_float4(r, z, n, ghn);
       const float hnew = act ? hn : hreg;
       hreg = hnew;
-      unsigned hq = (unsigned)__builtin_bit_cast(unsigned short, (__bf16)hnew);
-      hq = hq == 0xffffu ? 0x7fc0u : hq;
-      const unsigned pr = hq | ((unsigned)__builtin_amdgcn_update_dpp(0, (int)hq, 0x101, 0xf, 0xf, false) << 16);
-      const int q1 = __builtin_amdgcn_update_dpp(0, (int)pr, 0x102, 0xf, 0xf, false);
-      const int q2 = __builtin_amdgcn_update_dpp(0, (int)pr, 0x104, 0xf, 0xf, false);
-      const int q3 = __builtin_amdgcn_update_dpp(0, (int)pr, 0x106, 0xf, 0xf, false);
+      const i32x4 v = pack_h(hnew);
       if (ab) break;
       if ((lane & 7) == 0 && erow_ok) {
-        const i32x4 v = {(int)pr, q1, q2, q3};
         const unsigned off2 = (unsigned)((((size_t)(s + 1) * NP + r0 + erow) * H + u0 + ec) * 2);
-        store_granule(plain, rs_hx, hxd, off2, v);
+        store_granule(plain, rs_hx, off2, v);
       }
       oh_s[s & 1][erow][ec] = hnew;
       oy_s[s & 1][erow][ec] = act ? hn : 0.f;
@@ -1199,10 +988,7 @@ __global__ __launch_bounds__(QTH) void rnne_fwd_kernel(XFwd a) {
   } else {
     for (int s = 0; s < a.steps; ++s) {
       st.mark(-1);
-      if (a.ysum != nullptr && s >= 2) mw_ysum_load(s - 2);
-      if (s + 1 < a.steps) mw_put(s + 1);
-      if (s >= 2) mw_store(s - 2);
-      if (s + 2 < a.steps) mw_load(s + 2);
+      mw_step(s, a.steps, a.ysum != nullptr, mw_ysum_load, mw_put, mw_store, mw_load);
       st.mark(0);
       lds_barrier();
       st.mark(1);
@@ -1212,18 +998,8 @@ __global__ __launch_bounds__(QTH) void rnne_fwd_kernel(XFwd a) {
     }
   }
   __syncthreads();
-  if (wave == QW && !s_abort) {
-    if (a.steps >= 2) {
-      if (a.ysum != nullptr) mw_ysum_load(a.steps - 2);
-      mw_store(a.steps - 2);
-    }
-    if (a.steps >= 1) {
-      if (a.ysum != nullptr) mw_ysum_load(a.steps - 1);
-      mw_store(a.steps - 1);
-    }
-  }
-  if (STAMPS && wave == stw) { st.acc[5] = (unsigned long long)(s_mode + 10); st.store(a.stamps, 0); }
-  if (STAMPS && wave == QW && st.on) { a.stamps[(size_t)blockIdx.x * 8 + 6] = st.acc[0]; a.stamps[(size_t)blockIdx.x * 8 + 7] = st.acc[1]; }
+  if (wave == QW && !s_abort) mw_drain(a.steps, a.ysum != nullptr, mw_ysum_load, mw_store);
+  stamp_flush(st, a.stamps, wave, stw, QW, s_mode);
 }
 
 constexpr int DS2_BWD_CH = 3;     // R > 8 reduce-scatter gather: producers' granules in flight per lane (0 = all; H = 1280 BPTT 6.78 -> 6.63 us/step at 3, 6.65 at 2 and 4)
@@ -1285,14 +1061,7 @@ struct XBwdRS {
   unsigned long long* stamps;
 };
 
-// bf16x2_tagged / granule_tagged16 (tagged bf16 partials of the reduce-scatter ring): common.h
-
-// A ring word carries its use tag in the mantissa LSB (see rnnrs_bwd_kernel): the granule is
-// ready when all four words carry the expected tag.
-__device__ __forceinline__ bool granule_tagged(i32x4 v, unsigned tag) {
-  return (((unsigned)v[0] & 1u) == tag) && (((unsigned)v[1] & 1u) == tag) && (((unsigned)v[2] & 1u) == tag) &&
-         (((unsigned)v[3] & 1u) == tag);
-}
+// bf16x2_tagged / granule_tagged16: common.h; granule_tagged, ring_tag, ring_off16: rnn_exchange.h
 __device__ __forceinline__ float canon32(float f) { return (f != f) ? __uint_as_float(0x7fc00000u) : f; }
 
 template <int CELL, int MTU, int GPT, int PBF>
@@ -1322,13 +1091,9 @@ __global__ __launch_bounds__(NTH) void rnnrs_bwd_kernel(XBwdRS a) {
   const int H = a.H, GH = G * H, N = a.N, NP = a.NP, R = a.R, P = a.P, MTS = H / 16;
   const int bg = grp % a.BG, dir = grp / a.BG;
   const int r0 = bg * R, u0 = mem * UPW;
-  if (tid < ROWS) len_s[tid] = (tid < R && r0 + tid < N) ? a.lens[r0 + tid] : 0;
+  group_lens(len_s, a, r0, R, N);
   for (int i = tid; i < ROWS * DGP; i += NTH) (&dg_s[0][0])[i] = 0;
-  if (wave == 0) {
-    int m = group_census(a.census, grp, mem, P, a.timeout, a.err);
-    if ((a.knobs & 32768) && m > 0) m = 0;      // knob 32768: force write-through (timing)
-    if (lane == 0) { s_mode = m; s_abort = (m < 0); }
-  }
+  group_mode<32768>(s_mode, s_abort, a, grp, mem, P, wave);   // knob 32768: write-through
 
   // resident A fragments of the worker waves: A[m][k] = U[g*H + u0 + k][16*mt + m],
   // m-tile mt = wave + 7*i, k-step g (this workgroup's 32 columns of gate g)
@@ -1364,6 +1129,10 @@ __global__ __launch_bounds__(NTH) void rnnrs_bwd_kernel(XBwdRS a) {
   __syncthreads();   // len_s, dg_s zero rows, census
 
   // memory wave: per-step inputs (dy, gates, h_prev) one step ahead, dgx / dgh stores,
+  // (the three BPTT memory waves differ in what they move: G gates with gates / h_prev here, one
+  // gate and the H clamp in rnnw_bwd_kernel, pre-quantised dgx in rnnf8_bwd_kernel; their step
+  // loop also differs: a stamp between put and store here, the abort test before or after
+  // barrier #2. They stay per kernel.)
   // all in 8- / 16-B pieces: load task = (row, 4 units), store task = (row, gate, 8 units)
   constexpr int LT = ROWS * 8 / 64, ST = (ROWS * G * 4 + 63) / 64;
   uint2 pdy[LT];
@@ -1463,16 +1232,8 @@ __global__ __launch_bounds__(NTH) void rnnrs_bwd_kernel(XBwdRS a) {
   auto ring_off = [&](int slot, int j, int mt, int row, int u16) -> unsigned {
     return (unsigned)(((((((size_t)slot * a.BG + bg) * P + j) * MTS + mt) * R + row) * 16) + u16) * 4u;
   };
-  // use tag of P(s): slot s % 3 is written at processing index k = steps-1-s, so its uses
-  // are k, k+3, k+6, ... and (k / 3) & 1 alternates between consecutive uses; the ring is
-  // filled with 0xFFFFFFFF (tag 1) and every slot's first use has tag 0
-  auto tag_of = [&](int s) -> unsigned { return (unsigned)(((a.steps - 1 - s) / 3) & 1); };
-  // bf16 layout [slot][bg][producer][unit pair p][row][g 0..3][8 bf16]: granule (row, g) of
-  // pair p holds units 32p + {4g..4g+3, 16+4g..16+4g+3}
+  // use tag of P(s) and the bf16 ring layout: ring_tag / ring_off16 (rnn_exchange.h)
   const int NPR = MTS / 2;
-  auto ring_off16 = [&](int slot, int j, int pr, int row, int g) -> unsigned {
-    return (unsigned)((((((size_t)slot * a.BG + bg) * P + j) * NPR + pr) * R + row) * 4 + g) * 16u;
-  };
 
   if (wave < MW) {
     // pre-gather sleep (ops/rnn.py poll_default), s_sleep 1 units; bit 29: units of 4 (the wide
@@ -1490,7 +1251,7 @@ __global__ __launch_bounds__(NTH) void rnnrs_bwd_kernel(XBwdRS a) {
         float acc8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (has_next && grow < R) {
           const int cs = (s + 1) % 3;
-          const unsigned want = tag_of(s + 1);
+          const unsigned want = ring_tag(a.steps, s + 1);
           unsigned off[GPT];
           i32x4 v[GPT];
           // at most CHB producers' granules in flight per lane (DS2_BWD_CH; 0 = all)
@@ -1498,7 +1259,7 @@ __global__ __launch_bounds__(NTH) void rnnrs_bwd_kernel(XBwdRS a) {
 #pragma unroll
           for (int i = 0; i < GPT; ++i) {
             const int j = min(pg7 + MW * i, P - 1);
-            off[i] = ring_off16(cs, j, mem, grow, gg);
+            off[i] = ring_off16(a.BG, bg, P, NPR, R, cs, j, mem, grow, gg);
             if (i < CHB) v[i] = load_sc1_b128(rs_ring, off[i]);
           }
           const long long t0 = __builtin_amdgcn_s_memrealtime();
@@ -1533,14 +1294,14 @@ __global__ __launch_bounds__(NTH) void rnnrs_bwd_kernel(XBwdRS a) {
         float acc8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (has_next && grow < R) {
           const int cs = (s + 1) % 3;
-          const unsigned want = tag_of(s + 1);
+          const unsigned want = ring_tag(a.steps, s + 1);
           constexpr int NI = GPT / 2;
           unsigned off[NI];
           i32x4 v[NI];
 #pragma unroll
           for (int i = 0; i < NI; ++i) {
             const int j = min(pg7 + MW * (2 * i + h), P - 1);
-            off[i] = ring_off16(cs, j, mem, grow, gg);
+            off[i] = ring_off16(a.BG, bg, P, NPR, R, cs, j, mem, grow, gg);
             v[i] = load_sc1_b128(rs_ring, off[i]);
           }
           const long long t0 = __builtin_amdgcn_s_memrealtime();
@@ -1574,7 +1335,7 @@ __global__ __launch_bounds__(NTH) void rnnrs_bwd_kernel(XBwdRS a) {
         f32x4 acc4 = f32x4{0.f, 0.f, 0.f, 0.f};
         if (has_next) {
           const int cs = (s + 1) % 3;
-          const unsigned want = has_next ? tag_of(s + 1) : 0u;
+          const unsigned want = has_next ? ring_tag(a.steps, s + 1) : 0u;
           unsigned off[GPT];
           i32x4 v[GPT];
 #pragma unroll
@@ -1677,7 +1438,7 @@ __global__ __launch_bounds__(NTH) void rnnrs_bwd_kernel(XBwdRS a) {
       // (M) publish P(s) = dgh_s[:, own cols] . U[own cols, :] into ring slot s % 3
       if (s > 0) {
         const int ws = s % 3;
-        const unsigned tg = tag_of(s);
+        const unsigned tg = ring_tag(a.steps, s);
         const unsigned tagmask = tg ? 0x00010001u : 0u;
         const bool prow = (lane & 15) < R;
         bf16x8 bfr[G];
@@ -1708,16 +1469,14 @@ __global__ __launch_bounds__(NTH) void rnnrs_bwd_kernel(XBwdRS a) {
             constexpr int NP = MTU / 2;
             unsigned offp[NP];
 #pragma unroll
-            for (int k = 0; k < NP; ++k) offp[k] = ring_off16(ws, mem, wave + MW * k, lane & 15, lane >> 4);
+            for (int k = 0; k < NP; ++k)
+              offp[k] = ring_off16(a.BG, bg, P, NPR, R, ws, mem, wave + MW * k, lane & 15, lane >> 4);
             // the store flavour is a compile-time branch of the whole loop (a runtime one per
             // store cost a select + compare + 3 scalar branches per pair)
             auto publish = [&](auto PLAIN) {
             auto store_pair = [&](int k, const f32x4& a0, const f32x4& a1) {
               if (prow && 2 * (wave + MW * k) + 1 < MTS) {
-                const i32x4 v = {(int)bf16x2_tagged(a0[0], a0[1], tagmask), (int)bf16x2_tagged(a0[2], a0[3], tagmask),
-                                 (int)bf16x2_tagged(a1[0], a1[1], tagmask), (int)bf16x2_tagged(a1[2], a1[3], tagmask)};
-                if constexpr (decltype(PLAIN)::value) store_b128(rs_ring, offp[k], v);
-                else store_sc1_b128(rs_ring, offp[k], v);
+                publish_pair<decltype(PLAIN)::value>(rs_ring, offp[k], a0, a1, tagmask);
               }
             };
             // a pair past MTS multiplies the zero fragments loaded for it and is not stored
@@ -1754,7 +1513,7 @@ __global__ __launch_bounds__(NTH) void rnnrs_bwd_kernel(XBwdRS a) {
                 for (int q = 0; q < 4; ++q)
                   v[q] = (int)bf16x2_tagged(q < 2 ? a0[2 * q] : a1[2 * q - 4], q < 2 ? a0[2 * q + 1] : a1[2 * q - 3],
                                             tagmask);
-                const unsigned off = ring_off16(ws, mem, pr, lane & 15, lane >> 4);
+                const unsigned off = ring_off16(a.BG, bg, P, NPR, R, ws, mem, pr, lane & 15, lane >> 4);
                 if (plain) store_b128(rs_ring, off, v);
                 else store_sc1_b128(rs_ring, off, v);
               }
@@ -1806,8 +1565,7 @@ __global__ __launch_bounds__(NTH) void rnnrs_bwd_kernel(XBwdRS a) {
     if (a.steps >= 2) mw_store(1);
     if (a.steps >= 1) mw_store(0);
   }
-  if (wave == 0) { st.acc[5] = (unsigned long long)(s_mode + 10); st.store(a.stamps, 0); }
-  if (wave == MEMW && st.on) { a.stamps[(size_t)blockIdx.x * 8 + 6] = st.acc[0]; a.stamps[(size_t)blockIdx.x * 8 + 7] = st.acc[1]; }
+  stamp_flush(st, a.stamps, wave, 0, MEMW, s_mode);
 
   // bias gradients: reduce the epilogue waves' rows through LDS, one read-modify-write
   // per (gate, unit) of the workgroup's own [bg] partial row
@@ -1892,15 +1650,12 @@ __global__ __launch_bounds__(QTH) void rnnw_fwd_kernel(XFwd a) {
   const int r0 = bg * R, u0 = mem * UWW;
   const int ke = wave;                            // K-eighth (MFMA waves)
   const int tw = wave >> 1, j0 = 2 * (wave & 1);  // owned tile and first owned element
-  if (tid < ROWS) len_s[tid] = (tid < R && r0 + tid < N) ? a.lens[r0 + tid] : 0;
-  if (wave == 0) {
-    const int m = group_census(a.census, grp, mem, a.P, a.timeout, a.err);
-    if (lane == 0) { s_mode = m; s_abort = (m < 0); }
-  }
+  group_start(len_s, s_mode, s_abort, a, r0, R, N, grp, mem, a.P, wave);
   __syncthreads();
   if (s_abort) return;
 
-  // memory wave: gx granule q -> (row, 8-unit chunk)
+  // memory wave: gx granule q -> (row, 8-unit chunk). Its own bodies: one gate, 64 units, the H
+  // clamp of a half-empty last workgroup and no y staging; the schedule is the shared one
   i32x4 gpre[RGL];
   auto mw_load = [&](int s) {
 #pragma unroll
@@ -1960,46 +1715,17 @@ __global__ __launch_bounds__(QTH) void rnnw_fwd_kernel(XFwd a) {
           if (a.ysum == nullptr) {
             *reinterpret_cast<uint2*>(a.y[dir] + ((size_t)t * N + b) * H + u) = o;
           } else {
-            // fused direction sum: same protocol as rnnq_fwd_kernel (the later producer of a
-            // position waits for the other's bf16 value and stores the rounded bf16 sum)
+            // fused direction sum: dirsum_store (rnn_exchange.h)
             unsigned long long* p = ysum_ptr(s, j);
             const int other = (s < L) ? (L - 1 - s) : s;
             const bool later = s > other || (s == other && dir == 1);
-            auto canon = [](unsigned h) { return (h & 0xffffu) == 0xffffu ? 0x7fc0u : (h & 0xffffu); };
-            if (!later) {
-              o.x = canon(o.x) | (canon(o.x >> 16) << 16);
-              o.y = canon(o.y) | (canon(o.y >> 16) << 16);
-              __hip_atomic_store(p, ((unsigned long long)o.y << 32) | o.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-              const long long t0 = __builtin_amdgcn_s_memrealtime();
-              unsigned long long q = yq[j];
-              while (true) {
-                const unsigned w0 = (unsigned)q, w1 = (unsigned)(q >> 32);
-                const bool ready = ((~w0 - 0x00010001u) & w0 & 0x80008000u) == 0 &&
-                                   ((~w1 - 0x00010001u) & w1 & 0x80008000u) == 0;
-                if (ready) break;
-                if (__builtin_amdgcn_s_memrealtime() - t0 > a.timeout) { atomicOr(a.err, 4u); break; }
-                __builtin_amdgcn_s_sleep(2);
-                q = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              }
-              const unsigned q0 = (unsigned)q, q1 = (unsigned)(q >> 32);
-              auto add2 = [](unsigned x, unsigned y) {
-                const unsigned lo = f2bf(__uint_as_float(x << 16) + __uint_as_float(y << 16));
-                const unsigned hi = f2bf(__uint_as_float(x & 0xffff0000u) + __uint_as_float(y & 0xffff0000u));
-                return lo | (hi << 16);
-              };
-              *reinterpret_cast<uint2*>(p) = make_uint2(add2(o.x, q0), add2(o.y, q1));
-            }
+            dirsum_store(p, o, yq[j], later, a);
           }
         }
       }
     }
   };
-  if (wave == QW) {
-    mw_load(0);
-    mw_put(0);
-    if (a.steps > 1) mw_load(1);
-  }
+  if (wave == QW) mw_prologue(a.steps, mw_load, mw_put);
   __syncthreads();   // gx ring slot 0
   const bool plain = s_mode == 1;
   const unsigned hx_bytes = (unsigned)((size_t)(a.steps + 1) * NP * H * 2);
@@ -2089,17 +1815,10 @@ __global__ __launch_bounds__(QTH) void rnnw_fwd_kernel(XFwd a) {
         const float hn = fminf(fmaxf(gxv[e] + pre, 0.f), RELU_CAP);
         const float hnew = act ? hn : hreg[e];
         hreg[e] = hnew;
-        unsigned hq = (unsigned)__builtin_bit_cast(unsigned short, (__bf16)hnew);
-        hq = hq == 0xffffu ? 0x7fc0u : hq;
-        // 16-B exchange granule = 8 consecutive units of one row = 8 consecutive lanes
-        const unsigned pr = hq | ((unsigned)__builtin_amdgcn_update_dpp(0, (int)hq, 0x101, 0xf, 0xf, false) << 16);
-        const int q1 = __builtin_amdgcn_update_dpp(0, (int)pr, 0x102, 0xf, 0xf, false);
-        const int q2 = __builtin_amdgcn_update_dpp(0, (int)pr, 0x104, 0xf, 0xf, false);
-        const int q3 = __builtin_amdgcn_update_dpp(0, (int)pr, 0x106, 0xf, 0xf, false);
+        const i32x4 v = pack_h(hnew);
         if ((lane & 7) == 0 && row < R && uok) {
-          const i32x4 v = {(int)pr, q1, q2, q3};
           const unsigned off2 = (unsigned)((((size_t)(s + 1) * NP + r0 + row) * H + u0 + lu) * 2);
-          store_granule(plain, rs_hx, hxd, off2, v);
+          store_granule(plain, rs_hx, off2, v);
         }
         oh_s[s & 1][row][lu] = hnew;
       }
@@ -2108,10 +1827,8 @@ __global__ __launch_bounds__(QTH) void rnnw_fwd_kernel(XFwd a) {
   } else {
     for (int s = 0; s < a.steps; ++s) {
       st.mark(-1);
-      if (a.ysum != nullptr && s >= 2) mw_ysum_load(s - 2);
-      if (s + 1 < a.steps) mw_put(s + 1);
-      if (s >= 2 && !(a.knobs & 2)) mw_store(s - 2);     // knob 2: no output stores (timing only)
-      if (s + 2 < a.steps) mw_load(s + 2);
+      mw_step(s, a.steps, a.ysum != nullptr, mw_ysum_load, mw_put, mw_store, mw_load,
+              !(a.knobs & 2));     // knob 2: no output stores (timing only)
       st.mark(0);
       lds_barrier();
       st.mark(1);
@@ -2119,18 +1836,8 @@ __global__ __launch_bounds__(QTH) void rnnw_fwd_kernel(XFwd a) {
     }
   }
   __syncthreads();
-  if (wave == QW && !s_abort) {
-    if (a.steps >= 2) {
-      if (a.ysum != nullptr) mw_ysum_load(a.steps - 2);
-      mw_store(a.steps - 2);
-    }
-    if (a.steps >= 1) {
-      if (a.ysum != nullptr) mw_ysum_load(a.steps - 1);
-      mw_store(a.steps - 1);
-    }
-  }
-  if (STAMPS && wave == 0) { st.acc[5] = (unsigned long long)(s_mode + 10); st.store(a.stamps, 0); }
-  if (STAMPS && wave == QW && st.on) { a.stamps[(size_t)blockIdx.x * 8 + 6] = st.acc[0]; a.stamps[(size_t)blockIdx.x * 8 + 7] = st.acc[1]; }
+  if (wave == QW && !s_abort) mw_drain(a.steps, a.ysum != nullptr, mw_ysum_load, mw_store);
+  stamp_flush(st, a.stamps, wave, 0, QW, s_mode);
 }
 
 // ------------------------------------------------------------------------------------
@@ -2166,12 +1873,9 @@ __global__ __launch_bounds__(NTH) void rnnw_bwd_kernel(XBwdRS a) {
   const int H = a.H, N = a.N, NP = a.NP, R = a.R, P = a.P, MTS = H / 16, NPR = MTS / 2;
   const int bg = grp % a.BG, dir = grp / a.BG;
   const int r0 = bg * R, u0 = mem * UWW;
-  if (tid < ROWS) len_s[tid] = (tid < R && r0 + tid < N) ? a.lens[r0 + tid] : 0;
+  group_lens(len_s, a, r0, R, N);
   for (int i = tid; i < ROWS * DGP; i += NTH) (&dg_s[0][0])[i] = 0;
-  if (wave == 0) {
-    const int m = group_census(a.census, grp, mem, P, a.timeout, a.err);
-    if (lane == 0) { s_mode = m; s_abort = (m < 0); }
-  }
+  group_mode(s_mode, s_abort, a, grp, mem, P, wave);
 
   // resident A fragments: A[m][k] = U[u0 + 32 kg + k][16 mt + m], m-tile mt of unit pair
   // wave + 7 (i >> 1) (tiles 2p, 2p + 1); own columns >= H (half-empty last workgroup) are 0
@@ -2265,13 +1969,7 @@ __global__ __launch_bounds__(NTH) void rnnw_bwd_kernel(XBwdRS a) {
   const size_t slot_floats = (size_t)a.BG * P * R * H;
   const unsigned ring_bytes = (unsigned)(3 * slot_floats * 4);
   const __amdgpu_buffer_rsrc_t rs_ring = make_rsrc(a.ring[dir], ring_bytes);
-  auto tag_of = [&](int s) -> unsigned { return (unsigned)(((a.steps - 1 - s) / 3) & 1); };
   StampT st(a.stamps != nullptr && (wave == 0 || wave == MEMW) && lane == 0);
-  // [slot][bg][producer][unit pair][row][granule g][8 bf16]: granule (row, g) of pair p holds
-  // units 32 p + {4 g .. 4 g + 3, 16 + 4 g .. 16 + 4 g + 3}
-  auto ring_off16 = [&](int slot, int j, int pr, int row, int g) -> unsigned {
-    return (unsigned)((((((size_t)slot * a.BG + bg) * P + j) * NPR + pr) * R + row) * 4 + g) * 16u;
-  };
 
   if (wave < MW) {
     const int presleep = (a.knobs >> 20) & 7;     // A/B: s_sleep 1 units before the gather
@@ -2291,7 +1989,7 @@ __global__ __launch_bounds__(NTH) void rnnw_bwd_kernel(XBwdRS a) {
           for (int q = 0; q < 8; ++q) acc8[pp][q] = 0.f;
         if (has_next && grow < R) {
           const int cs = (s + 1) % 3;
-          const unsigned want = tag_of(s + 1);
+          const unsigned want = ring_tag(a.steps, s + 1);
           unsigned off[2][NI];
           i32x4 v[2][NI];
 #pragma unroll
@@ -2299,7 +1997,7 @@ __global__ __launch_bounds__(NTH) void rnnw_bwd_kernel(XBwdRS a) {
 #pragma unroll
             for (int i = 0; i < NI; ++i) {
               const int j = min(wave + MW * (2 * i + h), P - 1);
-              off[pp][i] = ring_off16(cs, j, min(2 * mem + pp, NPR - 1), grow, gg);
+              off[pp][i] = ring_off16(a.BG, bg, P, NPR, R, cs, j, min(2 * mem + pp, NPR - 1), grow, gg);
               v[pp][i] = load_sc1_b128(rs_ring, off[pp][i]);
             }
           const long long t0 = __builtin_amdgcn_s_memrealtime();
@@ -2367,7 +2065,7 @@ __global__ __launch_bounds__(NTH) void rnnw_bwd_kernel(XBwdRS a) {
       // (M) publish P(s) = da_s[:, own cols] . U[own cols, :] into ring slot s % 3
       if (s > 0) {
         const int ws = s % 3;
-        const unsigned tagmask = tag_of(s) ? 0x00010001u : 0u;
+        const unsigned tagmask = ring_tag(a.steps, s) ? 0x00010001u : 0u;
         const bool prow = (lane & 15) < R;
         bf16x8 bfr[KG];
 #pragma unroll
@@ -2376,7 +2074,8 @@ __global__ __launch_bounds__(NTH) void rnnw_bwd_kernel(XBwdRS a) {
         constexpr int NPW = MTU / 2;
         unsigned offp[NPW];
 #pragma unroll
-        for (int k = 0; k < NPW; ++k) offp[k] = ring_off16(ws, mem, min(wave + MW * k, NPR - 1), lane & 15, lane >> 4);
+        for (int k = 0; k < NPW; ++k)
+          offp[k] = ring_off16(a.BG, bg, P, NPR, R, ws, mem, min(wave + MW * k, NPR - 1), lane & 15, lane >> 4);
         auto publish = [&](auto PLAIN) {
 #pragma unroll
           for (int k = 0; k < NPW; ++k) {
@@ -2388,10 +2087,7 @@ __global__ __launch_bounds__(NTH) void rnnw_bwd_kernel(XBwdRS a) {
               a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ua[2 * k + 1][kg], bfr[kg], a1, 0, 0, 0);
             }
             if (prow && wave + MW * k < NPR) {
-              const i32x4 v = {(int)bf16x2_tagged(a0[0], a0[1], tagmask), (int)bf16x2_tagged(a0[2], a0[3], tagmask),
-                               (int)bf16x2_tagged(a1[0], a1[1], tagmask), (int)bf16x2_tagged(a1[2], a1[3], tagmask)};
-              if constexpr (decltype(PLAIN)::value) store_b128(rs_ring, offp[k], v);
-              else store_sc1_b128(rs_ring, offp[k], v);
+              publish_pair<decltype(PLAIN)::value>(rs_ring, offp[k], a0, a1, tagmask);
             }
           }
         };
@@ -2418,8 +2114,7 @@ __global__ __launch_bounds__(NTH) void rnnw_bwd_kernel(XBwdRS a) {
     if (a.steps >= 2) mw_store(1);
     if (a.steps >= 1) mw_store(0);
   }
-  if (STAMPS && wave == 0) { st.acc[5] = (unsigned long long)(s_mode + 10); st.store(a.stamps, 0); }
-  if (STAMPS && wave == MEMW && st.on) { a.stamps[(size_t)blockIdx.x * 8 + 6] = st.acc[0]; a.stamps[(size_t)blockIdx.x * 8 + 7] = st.acc[1]; }
+  stamp_flush(st, a.stamps, wave, 0, MEMW, s_mode);
   // input-bias gradient: reduce the epilogue waves' rows through LDS
   if (a.dbx_part[dir] != nullptr && !s_abort) {
     float* bred = &red_s[0][0][0];

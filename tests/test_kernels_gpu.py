@@ -460,13 +460,18 @@ def test_fp8_quant2_direction_sum_is_torch_add_then_quant(cuda):
             assert torch.equal(x, y)
 
 
-@pytest.mark.parametrize("cell", ["gru", "rnn_relu"])
-def test_fused_direction_sum_bitwise(cuda, cell):
-    """The gen-4 forward's in-kernel direction sum (one direction writes its bf16 value, the
-    other adds) is bit-identical to y_fw + y_bw in bf16 via torch, variable lengths included."""
+@pytest.mark.parametrize("cell,H,N,T,family", [
+    pytest.param("gru", 800, 32, 57, 5, id="gru"),                  # rnne_fwd_kernel
+    pytest.param("rnn_relu", 800, 32, 57, 4, id="rnn_relu"),        # rnnq_fwd_kernel
+    pytest.param("gru", 1280, 8, 19, 4, id="gru-1280"),             # rnnq GRU, LDS k-steps, cross-XCD groups
+    pytest.param("rnn_relu", 1088, 8, 19, 6, id="rnn_relu-1088"),   # rnnw, half-empty last workgroup (1088 % 64 == 32)
+])
+def test_fused_direction_sum_bitwise(cuda, cell, H, N, T, family):
+    """The forwards' in-kernel direction sum (dirsum_store, csrc/rnn_exchange.h: one direction
+    writes its bf16 value, the other adds) is bit-identical to y_fw + y_bw in bf16 via torch,
+    variable lengths included, in each of the three kernels that call it."""
     from deepspeech_amd.ops import rnn as RNN
     torch.manual_seed(7)
-    N, H, T = 32, 800, 57
     G = RNN.GATES[cell]
     lens = torch.randint(T // 3, T + 1, (N,), dtype=torch.int32)
     lens[0] = T
@@ -478,6 +483,7 @@ def test_fused_direction_sum_bitwise(cuda, cell):
     assert plan.kind == "xcd"
     C = _ext_mod().ext()
     assert C.rnnx_fwd_fuses_sum(H, RNN.CELL_CODE[cell], 2, RNN.RNNX_KNOBS)
+    assert C.rnnx_fwd_family(H, RNN.CELL_CODE[cell], RNN.RNNX_KNOBS) == family   # the caller of dirsum_store under test
     old = RNN._FUSE_DIRSUM
     try:
         ys = []
