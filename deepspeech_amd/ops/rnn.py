@@ -657,10 +657,11 @@ def _prefill_bwd(plan: "RnnPlan", dev):
 
 
 def _run_bwd(dy, lens, U, hx, hs, gates, plan: RnnPlan, gstride: int, dgx_scale: float = 1.0,
-             want_bias: bool = True):
+             want_bias: bool = True, dgh=None, dgx=None):
     """Launch BPTT. Returns (dgx [T, N, gstride] bf16 (x dgx_scale), dgh [ndir, steps, NP, G*H],
     parts [k, ndir, BG, G*H] fp32 in-kernel bias-gradient partials: k=0 input bias, k=1 GRU
-    recurrent bias; None if want_bias is False)."""
+    recurrent bias; None if want_bias is False). dgh / dgx: preallocated outputs of those shapes
+    (the kernels write every element; tests pre-fill them), allocated here when None."""
     C = _ext.ext()
     T, N, H = dy.shape
     ndir, G = plan.ndir, GATES[plan.cell]
@@ -668,8 +669,10 @@ def _run_bwd(dy, lens, U, hx, hs, gates, plan: RnnPlan, gstride: int, dgx_scale:
     dev = dy.device
     d1 = ndir == 2
     dy = dy.to(torch.bfloat16).contiguous()
-    dgh = torch.empty(ndir, steps, plan.NP, G * H, device=dev, dtype=torch.bfloat16)
-    dgx = torch.empty(T, N, gstride, device=dev, dtype=torch.bfloat16)
+    if dgh is None:
+        dgh = torch.empty(ndir, steps, plan.NP, G * H, device=dev, dtype=torch.bfloat16)
+    if dgx is None:
+        dgx = torch.empty(T, N, gstride, device=dev, dtype=torch.bfloat16)
     gates = gates if gates.numel() > 0 else None
     geom = _geom(plan, T, N, gstride)
     if plan.kind == "xcd":
