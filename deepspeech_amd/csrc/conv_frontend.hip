@@ -144,7 +144,7 @@ template <int S0>
 __device__ __forceinline__ void conv2_fwd_body(const Conv2Fwd& a);
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv2_fwd_kernel(Conv2Fwd a) {
-  DS2_DCHECK(a.T2 == (a.T1 - C2_KT) / 2 + 1 && a.F2 == a.F1 - 4 && a.F1 <= C2F_PL && a.F1 > 64);
+  DS2_DCHECK(a.T2 == (a.T1 - C2_KT) / 2 + 1 && a.F2 == a.F1 - 4 && a.F1 <= C2F_PL && a.F1 >= 5);
   switch (uni(threadIdx.x >> 6)) {                   // k-step s = kt * 10 + kf * 2 + ci-half
     case 0: conv2_fwd_body<0>(a); break;
     case 1: conv2_fwd_body<C2F_KPW>(a); break;
@@ -195,7 +195,8 @@ __device__ __forceinline__ void conv2_fwd_body(const Conv2Fwd& a) {
   const int t_lo = (int)((long long)ntiles * xi / X), t_hi = (int)((long long)ntiles * (xi + 1) / X);
 
   // stage input rows 2 t2 .. 2 t2 + 9: plane p = (row p >> 2, 16-B channel chunk p & 3), round r
-  // = positions 64 r + lane (F1 in (64, 80]: 2 rounds). Wave w issues rounds k = w + 4 i of the
+  // = positions 64 r + lane (F1 in (64, 80]: 2 rounds; narrower rows leave round 1 empty and the
+  // positions past F1 unstaged). Wave w issues rounds k = w + 4 i of the
   // 80, i.e. planes (w >> 1) + 2 i in round w & 1: every offset but the tile base is a constant.
   constexpr int R = w & 1;
   const bool on = 64 * R + lane < F1;
@@ -270,7 +271,9 @@ __device__ __forceinline__ void conv2_fwd_body(const Conv2Fwd& a) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int f2 = 32 * m + 8 * w + 4 * hi + e;
-        if (m < 2 || f2 < a.F2) {
+        // every m: with F2 < 64 the positions F2..63 hold sums over unstaged LDS, and they must
+        // not enter the statistics (the row copy below never stored them)
+        if (f2 < a.F2) {
           const bf16_t b = f2bf(own[m][e] + bco);
           stg[f2 * CC + col] = b;
           const float vb = bf2f(b);

@@ -356,14 +356,23 @@ class FrontendCL(torch.autograd.Function):
         return None, gw1, gbias1, gg1, gb1, gw2, gbias2, gg2, gb2, None
 
 
+# F1 = (F0-5)//2+1 frequency positions each pass of csrc/conv_frontend.hip takes. The forward
+# kernels cover 9..80. A training step also runs ds2_conv2_dgrad, whose gate refuses F1 <= 64
+# (code -42: it stores positions 0..63 of a row unchecked), so training needs 65..80 (133..163
+# bins); every other kernel of the backward pass takes the forward range.
+CL_F1_FORWARD = (9, 80)
+CL_F1_TRAINING = (65, 80)
+
+
 def cl_supported(model, feats: torch.Tensor) -> bool:
-    """The channels-last MFMA front-end covers the reference geometry (32 filters and
-    F1 = (F0-5)/2+1 <= 80 frequency positions, i.e. up to 163 bins); other widths take the
-    library-conv path below."""
+    """The channels-last MFMA front-end covers the reference geometry (32 filters, at least 38
+    frames) at the widths every kernel of the pass about to run accepts; anything else takes
+    the library-conv path below."""
     if model.num_filters != 32 or feats.dim() != 3:
         return False
     F1 = (feats.shape[2] - 5) // 2 + 1
-    return 9 <= F1 <= 80 and feats.shape[1] >= 38
+    lo, hi = CL_F1_TRAINING if model.conv1.training else CL_F1_FORWARD
+    return lo <= F1 <= hi and feats.shape[1] >= 38
 
 
 def frontend_hip(model, feats: torch.Tensor) -> torch.Tensor:
