@@ -27,12 +27,12 @@ RESUME_KEYS = (
     "num_hidden", "num_rnn_layers", "rnn_type", "num_filters", "use_fp16",
     "temporal_stride", "initial_lr", "engine", "nchw",
     # extensions
-    "cell", "stack_fix", "seq_bn", "dtype", "ctc_collapse_repeated",
+    "cell", "stack_fix", "seq_bn", "dtype", "ctc_collapse_repeated", "lookahead",
 )
 EVAL_KEYS = (
     "num_hidden", "num_rnn_layers", "rnn_type", "num_filters", "use_fp16",
     "moving_avg_decay", "nchw",
-    "cell", "stack_fix", "seq_bn", "ctc_collapse_repeated",
+    "cell", "stack_fix", "seq_bn", "ctc_collapse_repeated", "lookahead",
 )
 
 
@@ -90,6 +90,9 @@ def build_train_parser() -> argparse.ArgumentParser:
                    help="Continue training from checkpoint directory")
     p.add_argument("--rnn_type", type=str, default="bidirectional",
                    help="unidirectional (uni-dir) or bidirectional")
+    p.add_argument("--lookahead", type=int, default=0,
+                   help="lookahead (row) convolution above the top recurrent layer: future frames "
+                        "seen, 0 = no such layer (1..31; each is 40 ms of streaming latency)")
     p.add_argument("--initial_lr", type=float, default=0.00001)
     p.add_argument("--num_filters", type=int, default=32)
     p.add_argument("--moving_avg_decay", type=float, default=0.9999)
@@ -256,6 +259,7 @@ def model_kwargs_from_args(args) -> Dict[str, Any]:
         stack_fix=getattr(args, "stack_fix", True),
         seq_bn=getattr(args, "seq_bn", "frozen"),
         layout="nchw" if str2bool(getattr(args, "nchw", True)) else "nhwc",
+        lookahead=int(getattr(args, "lookahead", 0) or 0),
     )
 
 

@@ -249,6 +249,22 @@ int ds2_hist_blocks(long long n);
 int ds2_hist_stats(const void* x, int bf16, long long n, unsigned* counts, float* part, int blocks, hipStream_t st);
 int ds2_spin(long long ticks, int blocks, int threads, int lds_bytes, int* done, hipStream_t st);
 
+// ---- lookahead.hip ----------------------------------------------------------------------
+// Lookahead (row) convolution: x, out bf16 [T, B, H] (H % 8 == 0, 16-B aligned), w bf16
+// [H, tau+1], 1 <= tau <= 31, lens [B]. bwd = 0: out = r from x = h; bwd = 1: out = dh from
+// x = dr. The weight gradient writes ds2_lookahead_wgrad_parts fp32 partials [P, H*(tau+1)] for
+// ds2_col_sum. The streaming step reads hist [tau, B, H] and x [n, B, H], writes out [n, B, H]
+// and rewrites hist. -60: shape outside the contract, -61: misaligned base, -62: weights
+// beyond the LDS.
+int ds2_lookahead(const void* x, const void* w, const int* lens, void* out, int T, int B, int H, int tau, int bwd,
+                  hipStream_t st);
+int ds2_lookahead_stream(void* hist, const void* x, const void* w, void* out, int n, int B, int H, int tau,
+                         hipStream_t st);
+int ds2_lookahead_wgrad_tpw(int T, int B, int H);
+int ds2_lookahead_wgrad_parts(int T, int B, int H);
+int ds2_lookahead_wgrad(const void* dr, const void* h, const int* lens, float* part, int T, int B, int H, int tau,
+                        hipStream_t st);
+
 // ---- conv_frontend.hip ------------------------------------------------------------------
 // optional BatchNorm-backward apply fused into conv1's weight-gradient staging
 struct DS2Conv1WgradBn {

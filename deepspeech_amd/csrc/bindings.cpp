@@ -1263,6 +1263,71 @@ void fc_logits(at::Tensor h, at::Tensor W, at::Tensor bias, at::Tensor logits) {
         "fc_logits");
 }
 
+// --------------------------------------------------------------------------- lookahead convolution (csrc/lookahead.hip)
+// Shapes every lookahead entry point shares: x bf16 [T, B, H], w bf16 [H, tau+1]; returns tau.
+int lookahead_dims(const at::Tensor& x, const at::Tensor& w, const char* what) {
+  need_gpu(x, what);
+  need_gpu(w, "lookahead w");
+  TORCH_CHECK(x.dim() == 3 && w.dim() == 2 && x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16,
+              "lookahead: bf16 [T, B, H] activations and bf16 [H, tau+1] weights");
+  const int64_t H = x.size(2), tau = w.size(1) - 1;
+  TORCH_CHECK(x.size(0) >= 1 && x.size(1) >= 1 && w.size(0) == H && H % 8 == 0 && tau >= 1 && tau <= 31,
+              "lookahead: H % 8 == 0, 1 <= tau <= 31, w [H, tau+1]");
+  return (int)tau;
+}
+
+const int* lookahead_lens(const at::Tensor& lens, const at::Tensor& x) {
+  need_gpu(lens, "lookahead lens");
+  TORCH_CHECK(lens.scalar_type() == at::kInt && lens.numel() == x.size(1), "lookahead: lens int32 [B]");
+  return lens.data_ptr<int>();
+}
+
+// out = r (bwd false, x = h) or dh (bwd true, x = dr)
+void lookahead(at::Tensor x, at::Tensor w, at::Tensor lens, at::Tensor out, bool bwd) {
+  const int tau = lookahead_dims(x, w, "lookahead x");
+  need_gpu(out, "lookahead out");
+  TORCH_CHECK(out.scalar_type() == at::kBFloat16 && out.sizes() == x.sizes(), "lookahead: out like x");
+  check(ds2_lookahead(x.data_ptr(), w.data_ptr(), lookahead_lens(lens, x), out.data_ptr(), (int)x.size(0),
+                      (int)x.size(1), (int)x.size(2), tau, bwd ? 1 : 0, cur_stream()),
+        "lookahead");
+}
+
+int64_t lookahead_wgrad_parts(int64_t T, int64_t B, int64_t H) {
+  return ds2_lookahead_wgrad_parts((int)T, (int)B, (int)H);
+}
+
+// part [P, H*(tau+1)] fp32, P = lookahead_wgrad_parts(T, B, H); tau is part's to tell
+void lookahead_wgrad(at::Tensor dr, at::Tensor h, at::Tensor lens, at::Tensor part, int64_t tau) {
+  need_gpu(dr, "lookahead dr");
+  need_gpu(h, "lookahead h");
+  need_gpu(part, "lookahead part");
+  TORCH_CHECK(dr.dim() == 3 && dr.scalar_type() == at::kBFloat16 && h.scalar_type() == at::kBFloat16 &&
+                  h.sizes() == dr.sizes() && dr.size(2) % 8 == 0 && tau >= 1 && tau <= 31 && dr.size(0) >= 1 &&
+                  dr.size(1) >= 1,
+              "lookahead_wgrad: bf16 dr, h [T, B, H], H % 8 == 0, 1 <= tau <= 31");
+  const int T = (int)dr.size(0), B = (int)dr.size(1), H = (int)dr.size(2);
+  TORCH_CHECK(part.scalar_type() == at::kFloat && part.dim() == 2 &&
+                  part.size(0) == ds2_lookahead_wgrad_parts(T, B, H) && part.size(1) == (int64_t)H * (tau + 1),
+              "lookahead_wgrad: part fp32 [lookahead_wgrad_parts, H*(tau+1)]");
+  check(ds2_lookahead_wgrad(dr.data_ptr(), h.data_ptr(), lookahead_lens(lens, dr), part.data_ptr<float>(), T, B, H,
+                            (int)tau, cur_stream()),
+        "lookahead_wgrad");
+}
+
+// one streaming step: out [n, B, H] from hist [tau, B, H] and x [n, B, H]; hist is rewritten
+void lookahead_stream(at::Tensor hist, at::Tensor x, at::Tensor w, at::Tensor out) {
+  const int tau = lookahead_dims(x, w, "lookahead x");
+  need_gpu(hist, "lookahead hist");
+  need_gpu(out, "lookahead out");
+  TORCH_CHECK(hist.scalar_type() == at::kBFloat16 && hist.dim() == 3 && hist.size(0) == tau &&
+                  hist.size(1) == x.size(1) && hist.size(2) == x.size(2) && out.scalar_type() == at::kBFloat16 &&
+                  out.sizes() == x.sizes(),
+              "lookahead_stream: hist bf16 [tau, B, H], out like x");
+  check(ds2_lookahead_stream(hist.data_ptr(), x.data_ptr(), w.data_ptr(), out.data_ptr(), (int)x.size(0),
+                             (int)x.size(1), (int)x.size(2), tau, cur_stream()),
+        "lookahead_stream");
+}
+
 // --------------------------------------------------------------------------- audio features (csrc/featurize.hip)
 int pcm_is_i16(const at::Tensor& pcm) {
   need_gpu(pcm, "pcm");
@@ -1487,6 +1552,10 @@ PYBIND11_MODULE(_C, m) {
         py::arg("label_lens"), py::arg("loss"), py::arg("G"), py::arg("ws"), py::arg("blank"), py::arg("zero_inf"),
         py::arg("mean") = py::none(), py::arg("counter") = py::none(), py::arg("first_bad") = py::none());
   m.def("fc_logits", &fc_logits);
+  m.def("lookahead", &lookahead);
+  m.def("lookahead_wgrad_parts", &lookahead_wgrad_parts);
+  m.def("lookahead_wgrad", &lookahead_wgrad);
+  m.def("lookahead_stream", &lookahead_stream);
   m.def("audio_stats", &audio_stats, py::arg("pcm"), py::arg("lens"), py::arg("offset"), py::arg("gain"));
   m.def("featurize", &featurize, py::arg("pcm"), py::arg("lens"), py::arg("offset"), py::arg("gain"),
         py::arg("basis"), py::arg("mel_idx"), py::arg("mel_w"), py::arg("dct"), py::arg("lifter"), py::arg("kind"),

@@ -18,6 +18,15 @@ arrives:
     launch per chunk, no log-prob copy), on the CPU the native runtime runs it (one host
     thread per stream group).
 
+Lookahead models (``DeepSpeech2(lookahead=tau)``): the lookahead convolution above the top
+recurrent layer gives output frame t the recurrent outputs of frames t .. t + tau, so the
+recogniser keeps the last tau recurrent outputs in a static buffer (``hist``, beside the
+recurrent states, inside the graph on the graph path) and every chunk of ``new`` recurrent frames
+yields the outputs of frames [done - tau, done - tau + new); those below 0 are dropped on the
+host. ``finish()`` pushes tau zero frames through to flush the last tau outputs. Frame t is still
+frame t (the time convention of align.py is unchanged); what accept() returns simply lags the
+audio by tau output frames of 40 ms each.
+
 Batched streams: ``StreamingRecognizer`` takes [B, T_chunk, F] chunks of B concurrent
 streams (equal chunk schedule, per-stream valid lengths), which is how a server batches.
 """
@@ -73,6 +82,9 @@ class StreamingRecognizer:
         self.use_graphs = bool(graphs) and self.dev.type == "cuda" and model.engine == "hip"
         self._graphs = {}
         self._h = None
+        # lookahead model: the last tau recurrent outputs (static, zeroed by reset())
+        self.tau = int(getattr(model, "lookahead", 0))
+        self._hist = None
         self.reset()
 
     def reset(self) -> None:
@@ -84,6 +96,10 @@ class StreamingRecognizer:
         if self._h is not None:
             for h in self._h:
                 h.zero_()
+        if self._hist is not None:
+            self._hist.zero_()
+        self.emitted = 0                    # output frames handed to the head and the decoder
+        self._flushed = False
         self.logprobs: List[torch.Tensor] = []
         self.beams = None
         self.gbeams = None
@@ -127,7 +143,11 @@ class StreamingRecognizer:
 
     @torch.no_grad()
     def accept(self, chunk: torch.Tensor) -> List[List[int]]:
-        """Feed [B, T_c, F] feature frames; returns the newly decoded (greedy) labels per stream."""
+        """Feed [B, T_c, F] feature frames; returns the newly decoded (greedy) labels per stream.
+        With a lookahead model they are the labels of the frames tau (40 ms each) before the ones
+        this chunk completed; the last tau frames come out of finish()."""
+        if self._flushed:
+            raise RuntimeError("the stream was finished; reset() starts a new one")
         t0 = time.perf_counter()
         m = self.model
         chunk = chunk.to(self.dev, torch.float32)
@@ -145,34 +165,19 @@ class StreamingRecognizer:
             feats = feats.to(m.compute_dtype)
         if not m.stack_fix:
             raise ValueError("streaming requires stack_fix=True")
+        # lookahead: this chunk yields frames [done - tau, done - tau + new); those below 0 go
+        drop = min(new, max(0, self.tau - self.done))
         if self.use_graphs:
-            lp, best_t = self._graph_chunk(feats.contiguous())
+            lp, best_t = self._graph_chunk(feats.contiguous(), drop)
         else:
             x = m.frontend(feats)                              # [new, B, C*F2]
             assert x.shape[0] == new, (x.shape, new)
             lens = torch.full((self.B,), new, dtype=torch.int32, device=self.dev)
             for i, layer in enumerate(m.rnn):
                 x, self.states[i] = self._layer(layer, x, lens, self.states[i])
-            logits = m.head(x).float()
-            lp = torch.log_softmax(logits, -1)                 # [new, B, K]
-            best_t = lp.argmax(-1)
-        assert lp.shape[0] == new, (lp.shape, new)
-        self.logprobs.append(lp)
-        best = best_t.cpu().numpy()                            # [new, B]
-        if self.gbeams is not None:
-            # prefix beam search advances chunk by chunk, beams resident on the device
-            self.gbeams.feed(lp)
-        elif self.beams is not None:
-            # prefix beam search advances chunk by chunk (beams carried in the native
-            # runtime, streams decoded on parallel host threads)
-            self.beams.feed(lp.cpu().numpy(), np.full((self.B,), new, dtype=np.int32))
-        for b in range(self.B):
-            for t in range(best.shape[0]):
-                s = int(best[t, b])
-                if s != self.last_sym[b] and s != BLANK:
-                    out[b].append(s)
-                self.last_sym[b] = s
-            self.greedy[b].extend(out[b])
+            lp, best_t = self._head(self._lookahead_step(x), drop)
+        assert (0 if lp is None else lp.shape[0]) == new - drop, (None if lp is None else lp.shape, new, drop)
+        out = self._emit(lp, best_t)
         self.done = t2_total
         # keep only the input frames future outputs can still see
         keep_from = STRIDE * self.done
@@ -187,40 +192,91 @@ class StreamingRecognizer:
             RNN.check_errors()        # after the chunk's sync: one 4-byte read
         return out
 
+    def _emit(self, lp, best_t) -> List[List[int]]:
+        """Hand the log-probs [n, B, K] of n more output frames to the stored log-probs, the beam
+        search and the greedy merge; returns the newly decoded (greedy) labels per stream."""
+        out: List[List[int]] = [[] for _ in range(self.B)]
+        if lp is None or lp.shape[0] == 0:
+            return out
+        n = lp.shape[0]
+        self.logprobs.append(lp)
+        best = best_t.cpu().numpy()                            # [n, B]
+        if self.gbeams is not None:
+            # prefix beam search advances chunk by chunk, beams resident on the device
+            self.gbeams.feed(lp)
+        elif self.beams is not None:
+            # prefix beam search advances chunk by chunk (beams carried in the native
+            # runtime, streams decoded on parallel host threads)
+            self.beams.feed(lp.cpu().numpy(), np.full((self.B,), n, dtype=np.int32))
+        for b in range(self.B):
+            for t in range(best.shape[0]):
+                s = int(best[t, b])
+                if s != self.last_sym[b] and s != BLANK:
+                    out[b].append(s)
+                self.last_sym[b] = s
+            self.greedy[b].extend(out[b])
+        self.emitted += n
+        return out
+
+    def _lookahead_step(self, x):
+        """Recurrent outputs x [n, B, H] of n more frames -> the lookahead layer's outputs of the n
+        frames tau before them (x itself for a model without the layer); ``hist`` carries the
+        last tau recurrent outputs to the next call, in place (capturable)."""
+        if self.tau == 0:
+            return x
+        m = self.model
+        if self._hist is None:
+            self._hist = torch.zeros(self.tau, self.B, x.shape[2], device=self.dev, dtype=x.dtype)
+        if m.engine == "hip":
+            from .ops import lookahead as LA
+            return LA.lookahead_stream(self._hist, x.contiguous(), LA.shadow_of(m.lookahead_weight))
+        return R.lookahead_stream_ref(self._hist, x, m.lookahead_weight)
+
+    def _head(self, x, drop: int):
+        """(log-probs, argmax) of the frames of x [n, B, H] after the first ``drop``; (None, None)
+        when none is left (the first chunks of a lookahead stream)."""
+        x = x[drop:]
+        if x.shape[0] == 0:
+            return None, None
+        lp = torch.log_softmax(self.model.head(x).float(), -1)
+        return lp, lp.argmax(-1)
+
     # ---- HIP-graph path -------------------------------------------------------------
-    def _chunk_body(self, feats):
+    def _chunk_body(self, feats, drop: int):
         """The whole GPU part of a chunk on static state buffers (capturable: no host sync)."""
         m = self.model
         x = m.frontend(feats)
         lens = torch.full((self.B,), x.shape[0], dtype=torch.int32, device=self.dev)
         for i, layer in enumerate(m.rnn):
             x, _ = self._layer(layer, x, lens, self._h[i], out=self._h[i])   # state carried in place
-        lp = torch.log_softmax(m.head(x).float(), -1)
-        return lp, lp.argmax(-1)
+        return self._head(self._lookahead_step(x), drop)
 
-    def _graph_chunk(self, feats):
+    def _graph_chunk(self, feats, drop: int = 0):
         if self._h is None:
             self._h = [torch.zeros(self.B, layer.hidden, device=self.dev, dtype=torch.float32)
                        for layer in self.model.rnn]
-        key = tuple(feats.shape)
+        # the frames a lookahead stream drops at its start change what the graph computes
+        key = tuple(feats.shape) + (drop,)
         g = self._graphs.get(key)
+        clone = lambda t: None if t is None else t.clone()   # noqa: E731
         if g is None:
             # first chunk of this shape: run it eagerly (real result, warms plans/handles),
             # then capture the same work into a graph for every later chunk of this shape
-            lp, best = self._chunk_body(feats)
+            lp, best = self._chunk_body(feats, drop)
             static_in = feats.clone()
-            saved = [h.clone() for h in self._h]              # capture records, never runs
+            state = self._h + ([self._hist] if self._hist is not None else [])
+            saved = [h.clone() for h in state]                # capture records, never runs
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                out = self._chunk_body(static_in)
-            for h, s in zip(self._h, saved):
+                out = self._chunk_body(static_in, drop)
+            for h, s in zip(state, saved):
                 h.copy_(s)
             self._graphs[key] = (graph, static_in, out)
-            return lp.clone(), best.clone()
+            return clone(lp), clone(best)
         graph, static_in, out = g
         static_in.copy_(feats)
         graph.replay()
-        return out[0].clone(), out[1].clone()
+        return clone(out[0]), clone(out[1])
 
     def _layer(self, layer, x, lens, h0, out=None):
         """One uni-directional layer from state h0 [B, H]; returns (y, h_last [B, H]), h_last
@@ -243,13 +299,35 @@ class StreamingRecognizer:
     def finish(self) -> List[List[int]]:
         """Final transcript label ids per stream (beam search over the whole stream if the
         decoder is 'beam', otherwise the incremental greedy result). With an LM the streams
-        end here: the end-of-sentence term counts."""
+        end here: the end-of-sentence term counts. A lookahead stream ends here too: the last tau
+        output frames, which were waiting for recurrent outputs that will not come, are computed
+        against tau zero frames (what the whole-utterance layer sees past the end) and go through
+        the head and the decoder first, once; the stream then holds frames_out(total) log-prob
+        rows, and accept() refuses more input until reset()."""
+        self._flush_lookahead()
         final = self.lm is not None
         if self.gbeams is not None:
             return self.gbeams.best(final) if final else self.gbeams.best()
         if self.beams is None:
             return [list(g) for g in self.greedy]
         return self.beams.best(final) if final else self.beams.best()
+
+    def _flush_lookahead(self) -> None:
+        if self.tau == 0 or self._flushed:
+            return
+        self._flushed = True
+        if self.done == 0:
+            return
+        t0 = time.perf_counter()
+        H = self.model.num_hidden
+        dtype = self._hist.dtype if self._hist is not None else torch.float32
+        zeros = torch.zeros(self.tau, self.B, H, device=self.dev, dtype=dtype)
+        # outputs of frames [done - tau, done); those below 0 (a stream shorter than tau) go
+        lp, best_t = self._head(self._lookahead_step(zeros), max(0, self.tau - self.done))
+        self._emit(lp, best_t)
+        if self.dev.type == "cuda":
+            torch.cuda.synchronize(self.dev)
+        self.compute_s += time.perf_counter() - t0
 
     @torch.no_grad()
     def finish_timed(self):

@@ -215,14 +215,21 @@ class DeepSpeech2(nn.Module):
     def __init__(self, num_filters: int = 32, num_hidden: int = 1024, num_rnn_layers: int = 2,
                  cell: str = "rnn_relu", bidirectional: bool = True, stack_fix: bool = True,
                  seq_bn: str = "frozen", num_classes: int = NUM_CLASSES,
-                 freq_bins: int = FREQ_BINS, layout: str = "nchw"):
+                 freq_bins: int = FREQ_BINS, layout: str = "nchw", lookahead: int = 0):
         """layout 'nchw' = src/deepSpeech_NCHW.py (default, --nchw True); 'nhwc' =
         src/deepSpeech.py (--nchw False): moments+EMA conv BN (eps 1e-5) and, when
         bidirectional, two deep per-direction stacks (bidirectional_dynamic_rnn over a
         MultiRNNCell each, src/deepSpeech.py:165-185) summed only at the top. The NHWC
         graph's channels-last flatten of conv2 (feature f*C + c) is a fixed permutation of
         the first layer's input columns; it is applied at the checkpoint boundary
-        (utils/checkpoint.py), the compute layout is shared."""
+        (utils/checkpoint.py), the compute layout is shared.
+
+        lookahead = tau > 0 (at most 31): a lookahead (row) convolution (Deep Speech 2, section
+        3.7; ops/lookahead.py) between the recurrent stack and the FC head gives output frame t
+        the next tau recurrent outputs (of the direction sum, for a bidirectional model):
+        ``lookahead_weight`` [H, tau+1], no activation, no bias, initialised to the identity
+        (w[:, 0] = 1, the rest 0), so a fresh model computes what the model without the layer
+        computes. 0: no such layer and no such parameter."""
         super().__init__()
         if cell not in GATES:
             raise ValueError("cell must be one of %s" % list(GATES))
@@ -254,6 +261,14 @@ class DeepSpeech2(nn.Module):
         self.fc_weight = nn.Parameter(torch.empty(num_classes, num_hidden))
         self.fc_bias = nn.Parameter(torch.zeros(num_classes))
         he_trunc_normal_(self.fc_weight, [num_classes, num_hidden])
+        lookahead = int(lookahead)
+        if not 0 <= lookahead <= 31:
+            raise ValueError("lookahead must be in 0..31")
+        self.lookahead = lookahead
+        if lookahead > 0:
+            w = torch.zeros(num_hidden, lookahead + 1)
+            w[:, 0] = 1.0
+            self.lookahead_weight = nn.Parameter(w)
         self.engine = "ref"
         self.compute_dtype = torch.float32
         # activation summaries (reference _activation_summary at conv1 / conv2 / rnn / logits,
@@ -302,6 +317,8 @@ class DeepSpeech2(nn.Module):
         for i, layer in enumerate(self.rnn):
             in_dim = layer.fw.W.shape[1]
             out["rnn_cell_%d" % i] = dirs * 2.0 * N * t2 * G * H * (in_dim + H)
+        if self.lookahead > 0:
+            out["lookahead"] = 2.0 * N * t2 * H * (self.lookahead + 1)
         out["softmax_linear"] = 2.0 * N * t2 * H * self.num_classes
         return out
 
@@ -369,6 +386,10 @@ class DeepSpeech2(nn.Module):
         conv1 last) and, per recurrent layer, [W_fw; W_bw] and [b_fw; b_bw] packed back to
         back so the fused layer reads/writes both directions as one matrix."""
         groups = [[("fc_bias", self.fc_bias)], [("fc_weight", self.fc_weight)]]
+        if self.lookahead > 0:
+            # right after the head: the carried optimizer update reaches it with the head's chunk
+            # (Trainer._chunks), which is when the forward reads it
+            groups.append([("lookahead_weight", self.lookahead_weight)])
         for i in reversed(range(len(self.rnn))):
             layer = self.rnn[i]
             pre = "rnn.%d." % i
@@ -383,6 +404,19 @@ class DeepSpeech2(nn.Module):
             for pn in ("bn_beta", "bn_gamma", "bias", "weight"):
                 groups.append([("%s.%s" % (cname, pn), getattr(blk, pn))])
         return groups
+
+    def lookahead_conv(self, h: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+        """The lookahead convolution over the recurrent stack's output h [T, N, H] (h itself
+        for a model without the layer)."""
+        if self.lookahead == 0:
+            return h
+        if self.engine == "hip":
+            from ..ops.lookahead import LookaheadConv
+            r = LookaheadConv.apply(h, self.lookahead_weight, lens)
+        else:
+            r = R.lookahead_ref(h, self.lookahead_weight, lens)
+        self._tap("lookahead", r)
+        return r
 
     def head(self, h: torch.Tensor) -> torch.Tensor:
         if self.engine == "hip":
@@ -419,11 +453,12 @@ class DeepSpeech2(nn.Module):
         if self.engine == "ref" and feats.device.type == "cuda" and self.compute_dtype != torch.float32:
             with torch.autocast("cuda", dtype=self.compute_dtype):
                 x = self.frontend(feats)
-                h = self.recurrent(x, lens)
+                h = self.lookahead_conv(self.recurrent(x, lens), lens)
                 logits = self.head(h)
             return logits.float(), lens
         x = self.frontend(feats)
         h = self.recurrent(x, lens.to(x.device))
+        h = self.lookahead_conv(h, lens.to(x.device))
         logits = self.head(h)
         self._tap("softmax_linear", logits)
         return logits, lens
@@ -438,6 +473,7 @@ class DeepSpeech2(nn.Module):
             xin, lens = self._hip_inputs(feats, seq_lens)
             x = self.frontend(xin)
             h = self.recurrent(x, lens.to(x.device))
+            h = self.lookahead_conv(h, lens.to(x.device))
             from ..ops import rnn as RNN
             RNN.flush_transposes()      # the dx GEMMs' W^T shadows, beside the head + CTC
             if self.capture:

@@ -62,6 +62,38 @@ def time_mask(lens: torch.Tensor, T: int, dtype=torch.bool) -> torch.Tensor:
     return (t < lens.to(torch.long).unsqueeze(0)).to(dtype)
 
 
+def lookahead_ref(h: torch.Tensor, w: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+    """Lookahead (row) convolution (Deep Speech 2, section 3.7) over time-major h [T, B, H] with
+    w [H, tau+1] and valid(t, b) = t < min(lens[b], T):
+
+        r[t,b,i] = valid(t,b) ? sum_{j=0..tau, valid(t+j,b)} w[i,j] h[t+j,b,i] : 0
+
+    Linear, no bias; summed in ascending j in h's dtype (fp64 in: the oracle of the kernels)."""
+    T = h.shape[0]
+    m = time_mask(lens.to(h.device), T).unsqueeze(-1)                 # [T, B, 1]
+    hm = torch.where(m, h, torch.zeros((), dtype=h.dtype, device=h.device))
+    w = w.to(h.dtype)
+    r = torch.zeros_like(hm)
+    for j in range(min(w.shape[1], T)):
+        term = w[:, j] * hm[j:]
+        r = r + (term if j == 0 else F.pad(term, (0, 0, 0, 0, 0, j)))
+    return torch.where(m, r, torch.zeros((), dtype=h.dtype, device=h.device))
+
+
+def lookahead_stream_ref(hist: torch.Tensor, x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """One streaming step of the lookahead convolution: with s = [hist (tau frames); x (n frames)],
+    out[k] = sum_j w[:,j] s[k+j] for k < n, and hist is rewritten in place with the last tau
+    frames of s. Output k is the layer's output for the frame tau steps before input k."""
+    tau, n = hist.shape[0], x.shape[0]
+    s = torch.cat([hist, x.to(hist.dtype)], 0)
+    w = w.to(s.dtype)
+    out = torch.zeros_like(s[:n])
+    for j in range(tau + 1):
+        out = out + w[:, j] * s[j:j + n]
+    hist.copy_(s[n:])
+    return out
+
+
 def seq_batch_norm(y: torch.Tensor, lens: torch.Tensor, mode: str,
                    moving_mean: Optional[torch.Tensor] = None,
                    moving_var: Optional[torch.Tensor] = None,

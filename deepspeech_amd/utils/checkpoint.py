@@ -119,6 +119,8 @@ def tf_name_map(model: DeepSpeech2) -> List[Tuple[str, str, Callable, Callable]]
                 out.append(("%s/b_h" % scope, tp + ".b_h", ident, ident))
     out += [("softmax_linear/weights", "fc_weight", ident, ident),
             ("softmax_linear/biases", "fc_bias", ident, ident)]
+    if getattr(model, "lookahead", 0) > 0:
+        out.append(("lookahead/weights", "lookahead_weight", ident, ident))
     return out
 
 

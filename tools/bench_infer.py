@@ -4,6 +4,7 @@ beam-search decoder on one MI355X).
 
   python tools/bench_infer.py [--layers 5] [--hidden 800] [--seconds 20] [--chunks 0.25,0.5,1.0]
                               [--batches 1,32] [--decoders greedy,beam] [--audio] [--lm ORDER]
+                              [--lookahead TAU]
 
 RTF = compute seconds / audio seconds per stream (B concurrent streams share each chunk
 launch, so B streams at RTF r serve B * (1 / r) x real time). Random-init weights and
@@ -11,6 +12,8 @@ synthetic 161-bin features (no checkpoint or dataset offline). One JSON line per
 ``--audio`` streams synthetic int16 PCM through StreamingRecognizer.accept_audio instead, so the
 RTF includes the featurization (csrc/featurize.hip). ``--lm ORDER`` fuses a character n-gram LM
 of that order, trained on seeded synthetic text, into the beam decoder (deepspeech_amd/lm.py).
+``--lookahead TAU`` puts a lookahead convolution over TAU future frames above the recurrent stack
+(random weights); the RTF then includes its streaming step and the flush in finish().
 """
 import argparse
 import json
@@ -41,6 +44,8 @@ def main():
                     help="beam decoder with a character LM of this order (seeded synthetic text)")
     ap.add_argument("--lm_weight", type=float, default=0.8)
     ap.add_argument("--label_bonus", type=float, default=0.5)
+    ap.add_argument("--lookahead", type=int, default=0, metavar="TAU",
+                    help="lookahead convolution over TAU future frames (0: none)")
     a = ap.parse_args()
     lm = None
     if a.lm > 0:
@@ -52,7 +57,10 @@ def main():
     eng = a.engine if dev.type == "cuda" else "ref"
     torch.manual_seed(0)
     m = DeepSpeech2(num_filters=32, num_hidden=a.hidden, num_rnn_layers=a.layers, cell=a.cell,
-                    bidirectional=False).to(dev)
+                    bidirectional=False, lookahead=a.lookahead).to(dev)
+    if a.lookahead > 0:
+        with torch.no_grad():
+            m.lookahead_weight.normal_(0.0, (a.lookahead + 1) ** -0.5)
     m.set_engine(eng, torch.bfloat16 if eng == "hip" else torch.float32)
     rtf(m, seconds=2.0, chunk_s=0.5, batch=1, **extra)  # warm-up (plans, kernels, allocator)
     for B in [int(x) for x in a.batches.split(",")]:
@@ -64,7 +72,7 @@ def main():
                 r, _ = rtf(m, seconds=a.seconds, chunk_s=c, batch=B, decoder=d, beam_width=a.beam_width, **kw)
                 print(json.dumps({"metric": "streaming RTF (lower is better)", "model": "DS2 2xconv(32) + %dx uni-%s-%d"
                                   % (a.layers, a.cell.upper(), a.hidden), "engine": eng, "streams": B,
-                                  "chunk_s": c, "decoder": d, "beam_width": a.beam_width if d == "beam" else None,
+                                  "chunk_s": c, "decoder": d, "lookahead": a.lookahead, "beam_width": a.beam_width if d == "beam" else None,
                                   "rtf": round(r, 5), "x_realtime_per_stream": round(1.0 / r, 1) if r > 0 else None,
                                   "x_realtime_total": round(B / r, 1) if r > 0 else None,
                                   "audio_s": a.seconds, "data": data,
