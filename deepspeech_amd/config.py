@@ -122,6 +122,10 @@ def build_train_parser() -> argparse.ArgumentParser:
     p.add_argument("--log_every", type=int, default=10)
     p.add_argument("--nan_policy", type=str, default="abort", choices=["abort", "skip"])
     p.add_argument("--seed", type=int, default=1234)
+    p.add_argument("--specaug", type=str, default="",
+                   help="SpecAugment on the training batches (ops/specaug.py): a preset (ld, ls) or a spec "
+                        "such as F=27,nF=2,T=100,nT=2,p=0.2,W=0,fill=mean; empty = off. A training "
+                        "hyper-parameter: a resume may change it, evaluation never augments")
     p.add_argument("--device", type=str, default="auto", help="auto | cpu | cuda")
     p.add_argument("--gpus", type=int, default=None,
                    help="ranks (one per GPU) on this node; without an outer launcher (torchrun) the driver "

@@ -265,6 +265,21 @@ int ds2_lookahead_wgrad_parts(int T, int B, int H);
 int ds2_lookahead_wgrad(const void* dr, const void* h, const int* lens, float* part, int T, int B, int H, int tau,
                         hipStream_t st);
 
+// ---- specaug.hip ------------------------------------------------------------------------
+// SpecAugment on stored frames: x, out fp32 [B, T, F] (1 <= F <= 1024, 1 <= T <= 32767, B <= 65535),
+// lens int32 [B], plan int32 [B, 2 + 2 nF + 2 nT] = (w0, w, f0, fw, ..., t0, tw, ...), mean fp32
+// [B, F] or null (fill = zero). The plan kernel draws from Philox4x32-10 with key seed, counter
+// (block, first_utt + b, step) and takes any T, F >= 1. In place (x == out, plans without a warp
+// only) nothing is read and only masked cells of frames < lens are written. -70: shape outside
+// the contract, -71: policy outside its range (nF <= 8, nT <= 16, p_ppm <= 1000000), -72: inplace
+// set without x == out, or x == out without it.
+int ds2_specaug_plan(const int* lens, int* plan, int B, int T, int F, int nF, int Fw, int nT, int Tw, int p_ppm,
+                     int W, unsigned seed_lo, unsigned seed_hi, unsigned step_lo, unsigned step_hi,
+                     unsigned first_utt, hipStream_t st);
+int ds2_specaug_mean(const float* x, const int* lens, float* mean, int B, int T, int F, hipStream_t st);
+int ds2_specaug_apply(const float* x, const int* lens, const int* plan, const float* mean, float* out, int B, int T,
+                      int F, int nF, int nT, int inplace, hipStream_t st);
+
 // ---- conv_frontend.hip ------------------------------------------------------------------
 // optional BatchNorm-backward apply fused into conv1's weight-gradient staging
 struct DS2Conv1WgradBn {

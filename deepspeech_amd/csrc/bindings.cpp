@@ -1328,6 +1328,67 @@ void lookahead_stream(at::Tensor hist, at::Tensor x, at::Tensor w, at::Tensor ou
         "lookahead_stream");
 }
 
+// --------------------------------------------------------------------------- SpecAugment (csrc/specaug.hip)
+// plan int32 [B, 2 + 2 nF + 2 nT] from lens int32 [B]; seed, step and first_utt come as 32-bit words
+void specaug_plan(at::Tensor lens, at::Tensor plan, int64_t T, int64_t F, int64_t nF, int64_t Fw, int64_t nT,
+                  int64_t Tw, int64_t p_ppm, int64_t W, int64_t seed_lo, int64_t seed_hi, int64_t step_lo,
+                  int64_t step_hi, int64_t first_utt) {
+  const int64_t B = lens.numel();
+  const int* l = need_i32(lens, "specaug lens", B);
+  TORCH_CHECK(B >= 1 && B < (1LL << 31) && T >= 1 && T < (1LL << 31) && F >= 1 && F < (1LL << 31),
+              "specaug_plan: B, T, F in [1, 2^31)");
+  TORCH_CHECK(nF >= 0 && nF <= 8 && nT >= 0 && nT <= 16, "specaug_plan: nF <= 8, nT <= 16");
+  TORCH_CHECK(plan.dim() == 2 && plan.size(0) == B && plan.size(1) == 2 + 2 * nF + 2 * nT,
+              "specaug_plan: plan int32 [B, 2 + 2 nF + 2 nT]");
+  int* p = need_i32(plan, "specaug plan", 0);
+  const auto in32 = [](int64_t v) { return v >= 0 && v < (1LL << 31); };
+  TORCH_CHECK(in32(Fw) && in32(Tw) && in32(W) && in32(p_ppm), "specaug_plan: policy value out of range");
+  const auto word = [](int64_t v) {
+    TORCH_CHECK(v >= 0 && v <= 0xffffffffLL, "specaug_plan: seed / step / first_utt as 32-bit words");
+    return (unsigned)v;
+  };
+  check(ds2_specaug_plan(l, p, (int)B, (int)T, (int)F, (int)nF, (int)Fw, (int)nT, (int)Tw, (int)p_ppm, (int)W,
+                         word(seed_lo), word(seed_hi), word(step_lo), word(step_hi), word(first_utt), cur_stream()),
+        "specaug_plan");
+}
+
+void specaug_dims(const at::Tensor& x, const at::Tensor& lens, const char* what) {
+  need_gpu(x, what);
+  TORCH_CHECK(x.scalar_type() == at::kFloat && x.dim() == 3, what, " must be float32 [B, T, F]");
+  TORCH_CHECK(x.size(0) >= 1 && x.size(0) <= 65535 && x.size(1) >= 1 && x.size(1) <= 32767 && x.size(2) >= 1 &&
+                  x.size(2) <= 1024,
+              "specaug: B <= 65535, T <= 32767, F <= 1024");
+  need_i32(lens, "specaug lens", x.size(0));
+  TORCH_CHECK(lens.numel() == x.size(0), "specaug: lens int32 [B]");
+}
+
+void specaug_mean(at::Tensor x, at::Tensor lens, at::Tensor mean) {
+  specaug_dims(x, lens, "specaug x");
+  need_f32(mean, "specaug mean", x.size(0) * x.size(2));
+  TORCH_CHECK(mean.numel() == x.size(0) * x.size(2), "specaug_mean: mean float32 [B, F]");
+  check(ds2_specaug_mean(x.data_ptr<float>(), lens.data_ptr<int>(), mean.data_ptr<float>(), (int)x.size(0),
+                         (int)x.size(1), (int)x.size(2), cur_stream()),
+        "specaug_mean");
+}
+
+// out = SpecAugment(x) by plan; fill [B, F] or None (zeros); inplace: out is x and only masked cells are written
+void specaug_apply(at::Tensor x, at::Tensor lens, at::Tensor plan, OptT fill, at::Tensor out, int64_t nF, int64_t nT,
+                   bool inplace) {
+  specaug_dims(x, lens, "specaug x");
+  need_gpu(out, "specaug out");
+  TORCH_CHECK(out.scalar_type() == at::kFloat && out.sizes() == x.sizes(), "specaug_apply: out like x");
+  TORCH_CHECK(nF >= 0 && nF <= 8 && nT >= 0 && nT <= 16, "specaug_apply: nF <= 8, nT <= 16");
+  need_i32(plan, "specaug plan", x.size(0) * (2 + 2 * nF + 2 * nT));
+  TORCH_CHECK(plan.numel() == x.size(0) * (2 + 2 * nF + 2 * nT), "specaug_apply: plan int32 [B, 2 + 2 nF + 2 nT]");
+  const float* f = ptr_or_null<const float>(fill, "specaug fill");
+  if (f) TORCH_CHECK(fill->scalar_type() == at::kFloat && fill->numel() == x.size(0) * x.size(2),
+                     "specaug_apply: fill float32 [B, F]");
+  check(ds2_specaug_apply(x.data_ptr<float>(), lens.data_ptr<int>(), plan.data_ptr<int>(), f, out.data_ptr<float>(),
+                          (int)x.size(0), (int)x.size(1), (int)x.size(2), (int)nF, (int)nT, inplace ? 1 : 0,
+                          cur_stream()),
+        "specaug_apply");
+}
+
 // --------------------------------------------------------------------------- audio features (csrc/featurize.hip)
 int pcm_is_i16(const at::Tensor& pcm) {
   need_gpu(pcm, "pcm");
@@ -1556,6 +1617,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("lookahead_wgrad_parts", &lookahead_wgrad_parts);
   m.def("lookahead_wgrad", &lookahead_wgrad);
   m.def("lookahead_stream", &lookahead_stream);
+  m.def("specaug_plan", &specaug_plan);
+  m.def("specaug_mean", &specaug_mean);
+  m.def("specaug_apply", &specaug_apply, py::arg("x"), py::arg("lens"), py::arg("plan"), py::arg("fill"),
+        py::arg("out"), py::arg("nF"), py::arg("nT"), py::arg("inplace"));
   m.def("audio_stats", &audio_stats, py::arg("pcm"), py::arg("lens"), py::arg("offset"), py::arg("gain"));
   m.def("featurize", &featurize, py::arg("pcm"), py::arg("lens"), py::arg("offset"), py::arg("gain"),
         py::arg("basis"), py::arg("mel_idx"), py::arg("mel_w"), py::arg("dct"), py::arg("lifter"), py::arg("kind"),

@@ -19,6 +19,7 @@ from __future__ import annotations
 
 from typing import List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -330,3 +331,155 @@ def ctc_viterbi_ref(log_probs: torch.Tensor, lens, labels, label_lens, blank: in
             tok_score[b, l] = acc
     return (torch.from_numpy(path), torch.from_numpy(tok_start), torch.from_numpy(tok_end),
             torch.from_numpy(tok_score), torch.from_numpy(score))
+
+
+# ---- SpecAugment (ops/specaug.py, csrc/specaug.hip) ---------------------------------------
+PHILOX_M = (0xD2511F53, 0xCD9E8D57)
+PHILOX_W = (0x9E3779B9, 0xBB67AE85)
+SPECAUG_MEAN_SLICES = 32
+
+
+def philox4x32(ctr, key):
+    """Philox4x32-10: ``ctr`` four and ``key`` two 32-bit words (ints, or numpy arrays that
+    broadcast against each other); returns the four output words as uint64 arrays (ints for
+    int inputs)."""
+    scalar = all(isinstance(v, (int, np.integer)) for v in tuple(ctr) + tuple(key))
+    m32 = np.uint64(0xffffffff)
+    c = [np.asarray(v, np.uint64) & m32 for v in ctr]
+    k = [np.asarray(v, np.uint64) & m32 for v in key]
+    for _ in range(10):
+        p0 = np.uint64(PHILOX_M[0]) * c[0]
+        p1 = np.uint64(PHILOX_M[1]) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & m32, (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & m32]
+        k = [(k[0] + np.uint64(PHILOX_W[0])) & m32, (k[1] + np.uint64(PHILOX_W[1])) & m32]
+    return tuple(int(v) for v in c) if scalar else tuple(c)
+
+
+def specaug_plan_ref(lens, T: int, F: int, policy, seed: int, step: int, first_utt: int = 0) -> torch.Tensor:
+    """The SpecAugment plan [B, 2 + 2 nF + 2 nT] int32 = (w0, w, f0, fw, ..., t0, tw, ...) of
+    utterances first_utt .. first_utt + B - 1 at ``step``, in exact integer arithmetic.
+    ``policy`` has nF, Fw, nT, Tw, p_ppm, W. Block j of the generator has counter (j, u, step)
+    and key seed; word i of the stream is x[i]; a uniform integer in [0, n) is (x * n) >> 32."""
+    L = np.clip(np.asarray(torch.as_tensor(lens).cpu()).astype(np.int64).reshape(-1), 0, T)
+    B = L.shape[0]
+    nF, nT, W = int(policy.nF), int(policy.nT), int(policy.W)
+    ndraw = 2 + 2 * nF + 2 * nT
+    u = (int(first_utt) + np.arange(B, dtype=np.uint64)) & np.uint64(0xffffffff)
+    key = (seed & 0xffffffff, (seed >> 32) & 0xffffffff)
+    words = []
+    for j in range((ndraw + 3) // 4):
+        words.extend(philox4x32((np.uint64(j), u, np.uint64(step & 0xffffffff), np.uint64((step >> 32) & 0xffffffff)),
+                                (np.uint64(key[0]), np.uint64(key[1]))))
+    x = [np.broadcast_to(w, (B,)).astype(np.uint64) for w in words]
+
+    def mulhi(xw, n):                      # n int64 array or int, 0 <= n <= 2^32
+        return ((xw * np.asarray(n, np.int64).astype(np.uint64)) >> np.uint64(32)).astype(np.int64)
+
+    plan = np.zeros((B, ndraw), np.int64)
+    n0 = L - 2 * W - 2
+    warp = (n0 >= 1) & (W > 0)
+    plan[:, 0] = np.where(warp, W + 1 + mulhi(x[0], np.maximum(n0, 0)), 0)
+    plan[:, 1] = np.where(warp, mulhi(x[1], 2 * W + 1) - W, 0)
+    d = 2
+    for k in range(nF):
+        fw = mulhi(x[d], min(int(policy.Fw), F) + 1)
+        plan[:, 2 + 2 * k] = mulhi(x[d + 1], F - fw + 1)
+        plan[:, 3 + 2 * k] = fw
+        d += 2
+    c = np.minimum(int(policy.Tw), (L * int(policy.p_ppm)) // 1000000)
+    for k in range(nT):
+        tw = mulhi(x[d], c + 1)
+        plan[:, 2 + 2 * nF + 2 * k] = mulhi(x[d + 1], L - tw + 1)
+        plan[:, 3 + 2 * nF + 2 * k] = tw
+        d += 2
+    return torch.from_numpy(plan.astype(np.int32))
+
+
+def specaug_warp_index(lens: torch.Tensor, plan: torch.Tensor, T: int):
+    """Source of every output frame under the plan's warp: (i, r, den, valid), each [B, T] int64
+    (valid bool): out[t] = x[i] + (r / den) (x[i+1] - x[i]) for valid = t < L; i = t, r = 0 and
+    den = 1 in the padding and under the identity warp (w0 = 0)."""
+    dev = plan.device
+    L = lens.to(dev).long().clamp(0, T)[:, None]
+    t = torch.arange(T, device=dev)[None, :]
+    w0 = plan[:, 0:1].long()
+    d0 = w0 + plan[:, 1:2].long()
+    valid = t < L
+    plain = (w0 == 0) | ~valid
+    left = t <= d0
+    num = torch.where(left, t * w0, (t - d0) * (L - 1 - w0))
+    den = torch.where(left, d0, L - 1 - d0)
+    base = torch.where(left, torch.zeros_like(w0), w0)
+    den = torch.where(plain, torch.ones_like(den), den).clamp(min=1)
+    num = torch.where(plain, torch.zeros_like(num), num)
+    q = torch.div(num, den, rounding_mode="floor")
+    i = torch.where(plain, t.expand_as(num), base + q)
+    return i, num - q * den, den, valid
+
+
+def specaug_masks(lens: torch.Tensor, plan: torch.Tensor, T: int, F: int, nF: int):
+    """(time mask [B, T], frequency mask [B, F]) of a plan, both bool; the padding is in neither."""
+    dev = plan.device
+    t = torch.arange(T, device=dev)[None, :]
+    f = torch.arange(F, device=dev)[None, :]
+    tm = torch.zeros(plan.shape[0], T, dtype=torch.bool, device=dev)
+    fm = torch.zeros(plan.shape[0], F, dtype=torch.bool, device=dev)
+    for k in range(nF):
+        f0, fw = plan[:, 2 + 2 * k, None].long(), plan[:, 3 + 2 * k, None].long()
+        fm |= (f >= f0) & (f < f0 + fw)
+    for k in range((plan.shape[1] - 2 - 2 * nF) // 2):
+        t0, tw = plan[:, 2 + 2 * nF + 2 * k, None].long(), plan[:, 3 + 2 * nF + 2 * k, None].long()
+        tm |= (t >= t0) & (t < t0 + tw)
+    return tm & (t < lens.to(dev).long().clamp(0, T)[:, None]), fm
+
+
+def specaug_apply_ref(x: torch.Tensor, lens: torch.Tensor, plan: torch.Tensor, fill_values: Optional[torch.Tensor],
+                      nF: int) -> torch.Tensor:
+    """SpecAugment by ``plan`` on x [B, T, F], on x's device: fp64 arithmetic for an fp64 x (the
+    oracle), fp32 otherwise (the CPU path and the composite). Warp first, masks on warped frame
+    indices, frames >= L bit copies; masked cells take fill_values [B, F] (None: zeros) by
+    selection, whatever the input holds there."""
+    B, T, F = x.shape
+    ct = torch.float64 if x.dtype == torch.float64 else torch.float32
+    xc = x.to(ct)
+    plan = plan.to(x.device)
+    i, r, den, valid = specaug_warp_index(lens, plan, T)
+    a = torch.gather(xc, 1, i[:, :, None].expand(B, T, F))
+    if x.device.type != "cpu" or bool((plan[:, 0] != 0).any()):      # no host round trip on a GPU
+        b = torch.gather(xc, 1, (i + 1).clamp(max=T - 1)[:, :, None].expand(B, T, F))
+        q = (r.to(ct) / den.to(ct))[:, :, None]
+        a = torch.where((r == 0)[:, :, None], a, a + q * (b - a))
+    tm, fm = specaug_masks(lens, plan, T, F, nF)
+    fill = (torch.zeros(B, F, dtype=ct, device=x.device) if fill_values is None else fill_values.to(x.device, ct))
+    masked = (tm[:, :, None] | fm[:, None, :]) & valid[:, :, None]
+    out = torch.where(masked, fill[:, None, :].expand(B, T, F), a)
+    return torch.where(valid[:, :, None], out.to(x.dtype), x)
+
+
+def specaug_mean_ref(x: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+    """mean [B, F] of x [B, T, F] over frames t < L (0 for L == 0). fp64 x: the plain fp64 mean
+    (the oracle). Otherwise fp32 in the kernel's order: 32 partial sums over frames s, s + 32, ...
+    in ascending order, added pairwise, divided by float(L)."""
+    B, T, F = x.shape
+    Ls = np.clip(np.asarray(torch.as_tensor(lens).cpu()).astype(np.int64).reshape(-1), 0, T)
+    if x.dtype == torch.float64:
+        out = torch.zeros(B, F, dtype=torch.float64)
+        for b, L in enumerate(Ls):
+            if L:
+                out[b] = x[b, :L].sum(0) / float(L)
+        return out
+    xs = x.detach().to("cpu", torch.float32).numpy()
+    S = SPECAUG_MEAN_SLICES
+    out = np.zeros((B, F), np.float32)
+    for b, L in enumerate(Ls):
+        if L == 0:
+            continue
+        acc = np.zeros((S, F), np.float32)
+        full = L // S
+        for k in range(full):
+            acc += xs[b, k * S:(k + 1) * S]
+        acc[:L - full * S] += xs[b, full * S:L]
+        while acc.shape[0] > 1:
+            acc = acc[0::2] + acc[1::2]
+        out[b] = acc[0] / np.float32(L)
+    return torch.from_numpy(out)

@@ -189,6 +189,14 @@ def main(argv=None) -> int:
                       allreduce_bf16=args.allreduce_dtype == "bf16", nan_policy=args.nan_policy,
                       step_graphs={"auto": "auto", "on": True, "off": False}[args.step_graphs],
                       defer_update=True, dp_graphs=args.dp_step_graphs)
+    # --specaug: masks and warp drawn per (seed, global step, global utterance index), so a
+    # resumed run and any world size see the masks of the uninterrupted single-process run
+    aug = None
+    if args.specaug:
+        from .ops.specaug import SpecAugment, SpecAugPolicy
+        aug = SpecAugment(SpecAugPolicy.parse(args.specaug), args.seed)
+        if ctx.is_main:
+            print("specaug: ", aug.policy)
     start = 0
     rdir = resume_dir(args)
     if rdir is not None:
@@ -233,6 +241,11 @@ def main(argv=None) -> int:
             hb_ = data.next()
             return collapse_batch_labels(hb_) if args.ctc_collapse_repeated else hb_
     src = _Src()
+    if aug is not None and args.dummy and start > 0:
+        # an augmented synthetic run resumes its feed too (the generators are cheap to replay), so
+        # its steps are those of the uninterrupted run: the same batch under the same masks
+        for _ in range(start):
+            data.next()
     # GPU: batches are produced and uploaded by a background thread through a pinned ring
     # (data/prefetch.py), overlapping the previous steps' kernels
     prefetch = None
@@ -257,6 +270,9 @@ def main(argv=None) -> int:
             prof.__enter__()
         if batch is None:
             batch = to_device(hb, dev)
+        if aug is not None:
+            batch = dict(batch, feats=aug(batch["feats"], batch["seq_lens"], step,
+                                          first_utt=ctx.rank * args.batch_size))
         model.capture = sum_on and step % args.summary_every == 0
         loss = trainer.step(batch)
         model.capture = False
