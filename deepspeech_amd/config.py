@@ -83,7 +83,8 @@ def build_train_parser() -> argparse.ArgumentParser:
     g.add_argument("--use_fp16", dest="use_fp16", action="store_true")
     g.add_argument("--use_fp32", dest="use_fp16", action="store_false")
     p.set_defaults(use_fp16=False)
-    p.add_argument("--keep_prob", type=float, default=0.5, help="dropout keep prob (unused, Q8)")
+    p.add_argument("--keep_prob", type=float, default=0.5,
+                   help="dropout keep prob (unused, Q8; dropout between recurrent layers is --rnn_dropout)")
     p.add_argument("--num_hidden", type=int, default=1024, help="Number of hidden nodes")
     p.add_argument("--num_rnn_layers", type=int, default=2, help="Number of recurrent layers")
     p.add_argument("--checkpoint", type=str, default=None,
@@ -126,6 +127,13 @@ def build_train_parser() -> argparse.ArgumentParser:
                    help="SpecAugment on the training batches (ops/specaug.py): a preset (ld, ls) or a spec "
                         "such as F=27,nF=2,T=100,nT=2,p=0.2,W=0,fill=mean; empty = off. A training "
                         "hyper-parameter: a resume may change it, evaluation never augments")
+    p.add_argument("--rnn_dropout", type=float, default=0.0,
+                   help="dropout probability on what recurrent layer i hands to layer i+1 (ops/dropout.py; the "
+                        "top layer's output is not dropped), 0 = off. A training hyper-parameter: a resume "
+                        "may change it, evaluation never drops")
+    p.add_argument("--rnn_dropout_mode", type=str, default="element", choices=["element", "locked"],
+                   help="element: one draw per frame, utterance and unit; locked: one per utterance and "
+                        "unit, shared by all frames")
     p.add_argument("--device", type=str, default="auto", help="auto | cpu | cuda")
     p.add_argument("--gpus", type=int, default=None,
                    help="ranks (one per GPU) on this node; without an outer launcher (torchrun) the driver "

@@ -280,6 +280,16 @@ int ds2_specaug_mean(const float* x, const int* lens, float* mean, int B, int T,
 int ds2_specaug_apply(const float* x, const int* lens, const int* plan, const float* mean, float* out, int B, int T,
                       int F, int nF, int nT, int inplace, hipStream_t st);
 
+// ---- dropout.hip ------------------------------------------------------------------------
+// Dropout between recurrent layers: x, out bf16 [T, N, H] (H % 8 == 0, H <= 2^19, 16-B aligned,
+// T * N * H / 8 < 2^31); out == x runs in place. ctr int32 [2] on the device = (step, first_utt)
+// mod 2^32, read by the kernel. Element (t, b, i) is kept iff 16 bits of the Philox4x32-10 block
+// with key seed and counter (locked ? 0 : t, first_utt + b, step, 0x80000000 | locked << 30 |
+// site << 16 | i >> 3) are >= thr; kept: bf16(x * scale), dropped: +0. -80: shape outside the
+// contract, -81: misaligned, -82: site >= 16384, thr outside [1, 65535] or scale < 1.
+int ds2_seq_dropout(const void* x, void* out, const int* ctr, int T, int N, int H, unsigned seed_lo,
+                    unsigned seed_hi, int site, int thr, float scale, int locked, hipStream_t st);
+
 // ---- conv_frontend.hip ------------------------------------------------------------------
 // optional BatchNorm-backward apply fused into conv1's weight-gradient staging
 struct DS2Conv1WgradBn {

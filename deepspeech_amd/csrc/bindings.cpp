@@ -1389,6 +1389,28 @@ void specaug_apply(at::Tensor x, at::Tensor lens, at::Tensor plan, OptT fill, at
         "specaug_apply");
 }
 
+// --------------------------------------------------------------------------- dropout (csrc/dropout.hip)
+// out = dropout(x) under the mask of (seed, ctr = (step, first_utt) on the device, site); out may be x
+void seq_dropout(at::Tensor x, at::Tensor out, at::Tensor ctr, int64_t seed_lo, int64_t seed_hi, int64_t site,
+                 int64_t thr, double scale, bool locked) {
+  need_bf16(x, "seq_dropout x");
+  need_bf16(out, "seq_dropout out");
+  const int* c = need_i32(ctr, "seq_dropout ctr", 2);
+  TORCH_CHECK(x.dim() == 3 && out.sizes() == x.sizes() && x.size(0) >= 1 && x.size(1) >= 1 && x.size(2) >= 8 &&
+                  x.size(2) % 8 == 0 && x.size(2) <= 8 * 65536,
+              "seq_dropout: bf16 x, out [T, N, H], H % 8 == 0");
+  TORCH_CHECK(x.numel() / 8 < (1LL << 31), "seq_dropout: T * N * H / 8 < 2^31");
+  TORCH_CHECK(x.get_device() == out.get_device() && x.get_device() == ctr.get_device(), "seq_dropout: one device");
+  TORCH_CHECK(site >= 0 && site < 16384 && thr >= 1 && thr <= 65535, "seq_dropout: site < 16384, 1 <= thr <= 65535");
+  const auto word = [](int64_t v) {
+    TORCH_CHECK(v >= 0 && v <= 0xffffffffLL, "seq_dropout: the seed as 32-bit words");
+    return (unsigned)v;
+  };
+  check(ds2_seq_dropout(x.data_ptr(), out.data_ptr(), c, (int)x.size(0), (int)x.size(1), (int)x.size(2),
+                        word(seed_lo), word(seed_hi), (int)site, (int)thr, (float)scale, locked ? 1 : 0, cur_stream()),
+        "seq_dropout");
+}
+
 // --------------------------------------------------------------------------- audio features (csrc/featurize.hip)
 int pcm_is_i16(const at::Tensor& pcm) {
   need_gpu(pcm, "pcm");
@@ -1621,6 +1643,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("specaug_mean", &specaug_mean);
   m.def("specaug_apply", &specaug_apply, py::arg("x"), py::arg("lens"), py::arg("plan"), py::arg("fill"),
         py::arg("out"), py::arg("nF"), py::arg("nT"), py::arg("inplace"));
+  m.def("seq_dropout", &seq_dropout, py::arg("x"), py::arg("out"), py::arg("ctr"), py::arg("seed_lo"),
+        py::arg("seed_hi"), py::arg("site"), py::arg("thr"), py::arg("scale"), py::arg("locked"));
   m.def("audio_stats", &audio_stats, py::arg("pcm"), py::arg("lens"), py::arg("offset"), py::arg("gain"));
   m.def("featurize", &featurize, py::arg("pcm"), py::arg("lens"), py::arg("offset"), py::arg("gain"),
         py::arg("basis"), py::arg("mel_idx"), py::arg("mel_w"), py::arg("dct"), py::arg("lifter"), py::arg("kind"),

@@ -32,6 +32,7 @@
 // the fill by selection, so a NaN under a mask does not survive. The in-place variant (W == 0
 // only) reads nothing and writes only the masked cells of frames < L.
 #include "common.h"
+#include "philox.h"
 
 using namespace ds2;
 
@@ -52,21 +53,7 @@ struct Philox {
   unsigned k0, k1, u, s0, s1;
   unsigned x[4];
   int n;
-  __device__ __forceinline__ void block(unsigned j) {
-    unsigned c0 = j, c1 = u, c2 = s0, c3 = s1, a = k0, b = k1;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-      const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-      const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-      c0 = hi1 ^ c1 ^ a;
-      c1 = lo1;
-      c2 = hi0 ^ c3 ^ b;
-      c3 = lo0;
-      a += 0x9E3779B9u;
-      b += 0xBB67AE85u;
-    }
-    x[0] = c0, x[1] = c1, x[2] = c2, x[3] = c3;
-  }
+  __device__ __forceinline__ void block(unsigned j) { philox4x32_10(j, u, s0, s1, k0, k1, x); }
   __device__ __forceinline__ unsigned next() {
     if ((n & 3) == 0) block((unsigned)(n >> 2));
     return x[n++ & 3];

@@ -215,7 +215,8 @@ class DeepSpeech2(nn.Module):
     def __init__(self, num_filters: int = 32, num_hidden: int = 1024, num_rnn_layers: int = 2,
                  cell: str = "rnn_relu", bidirectional: bool = True, stack_fix: bool = True,
                  seq_bn: str = "frozen", num_classes: int = NUM_CLASSES,
-                 freq_bins: int = FREQ_BINS, layout: str = "nchw", lookahead: int = 0):
+                 freq_bins: int = FREQ_BINS, layout: str = "nchw", lookahead: int = 0,
+                 rnn_dropout: float = 0.0, rnn_dropout_mode: str = "element"):
         """layout 'nchw' = src/deepSpeech_NCHW.py (default, --nchw True); 'nhwc' =
         src/deepSpeech.py (--nchw False): moments+EMA conv BN (eps 1e-5) and, when
         bidirectional, two deep per-direction stacks (bidirectional_dynamic_rnn over a
@@ -229,7 +230,15 @@ class DeepSpeech2(nn.Module):
         the next tau recurrent outputs (of the direction sum, for a bidirectional model):
         ``lookahead_weight`` [H, tau+1], no activation, no bias, initialised to the identity
         (w[:, 0] = 1, the rest 0), so a fresh model computes what the model without the layer
-        computes. 0: no such layer and no such parameter."""
+        computes. 0: no such layer and no such parameter.
+
+        rnn_dropout = p in [0, 1): in training, the tensor recurrent layer i hands to layer i+1
+        is dropped with probability p (ops/dropout.py: a stateless Philox mask per (seed, step,
+        utterance, frame, unit, site), mode 'element', or 'locked' = one mask per utterance and
+        unit shared by all frames). The top layer's output is not dropped (nn.GRU's semantics),
+        so a one-layer model is unaffected; eval() is the identity. ``rnn_dropout_seed`` (an
+        attribute, default 0) keys the masks, ``dropout_state`` holds the step they are drawn
+        for (Trainer.step sets it)."""
         super().__init__()
         if cell not in GATES:
             raise ValueError("cell must be one of %s" % list(GATES))
@@ -269,6 +278,17 @@ class DeepSpeech2(nn.Module):
             w = torch.zeros(num_hidden, lookahead + 1)
             w[:, 0] = 1.0
             self.lookahead_weight = nn.Parameter(w)
+        from ..ops.reference import seq_dropout_threshold
+        if rnn_dropout_mode not in ("element", "locked"):
+            raise ValueError("rnn_dropout_mode must be element or locked")
+        self.rnn_dropout = float(rnn_dropout)
+        self.rnn_dropout_mode = rnn_dropout_mode
+        self.rnn_dropout_thr = seq_dropout_threshold(rnn_dropout)
+        if self.rnn_dropout_thr > 0 and not stack_fix:
+            # quirk Q1: no layer reads the previous layer's output, so there is nothing to drop
+            raise ValueError("rnn_dropout needs stack_fix=True")
+        self.rnn_dropout_seed = 0
+        self._dropout_state = None
         self.engine = "ref"
         self.compute_dtype = torch.float32
         # activation summaries (reference _activation_summary at conv1 / conv2 / rnn / logits,
@@ -350,7 +370,33 @@ class DeepSpeech2(nn.Module):
     def direction_stacks(self) -> bool:
         return self.layout == "nhwc" and self.bidirectional
 
+    @property
+    def dropout_state(self):
+        """The DropoutState (ops/dropout.py) of a model with rnn_dropout, on the parameters'
+        device (created at the first use there; None without dropout)."""
+        if self.rnn_dropout_thr == 0:
+            return None
+        dev = self.fc_weight.device
+        if self._dropout_state is None or self._dropout_state.ctr.device != dev:
+            from ..ops.dropout import DropoutState
+            self._dropout_state = DropoutState(dev)
+        return self._dropout_state
+
+    def _drop(self, h: torch.Tensor, layer: int, direction: int = 0) -> torch.Tensor:
+        """h = the output of recurrent layer ``layer`` on its way to layer + 1, dropped at site
+        2 * layer + direction."""
+        st = self.dropout_state
+        seed = self.rnn_dropout_seed & 0xffffffffffffffff
+        site, thr, mode = 2 * layer + direction, self.rnn_dropout_thr, self.rnn_dropout_mode
+        if self.engine == "hip":
+            from ..ops.dropout import seq_dropout
+            # the gradient that comes back is the fresh dx of layer + 1's projection GEMM
+            return seq_dropout(h, st, seed, site, thr, mode, grad_inplace=True)
+        step, first_utt = st.get()
+        return R.seq_dropout_ref(h, seed, step, first_utt, site, thr, mode == "locked")
+
     def recurrent(self, x: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+        drop = self.training and self.rnn_dropout_thr > 0
         if self.direction_stacks():
             x_f = x_b = x
             for i, layer in enumerate(self.rnn):
@@ -361,6 +407,8 @@ class DeepSpeech2(nn.Module):
                     from ..utils import trace as TR
                     with TR.phase(TR.rnn_cell(i)):
                         x_f, x_b = layer.forward_ref_split(x_f, x_b, lens)
+                if drop and i + 1 < len(self.rnn):
+                    x_f, x_b = self._drop(x_f, i, 0), self._drop(x_b, i, 1)
             out = x_f + x_b
             self._tap("rnn", out)
             return out
@@ -371,13 +419,17 @@ class DeepSpeech2(nn.Module):
                 from ..ops import rnn as RNN
                 # an fp8 layer feeding an fp8 layer hands over its two direction outputs and
                 # the upper layer's quantiser sums them (no direction-sum launch)
-                pair = self.stack_fix and i + 1 < len(self.rnn) and RNN.pairs_ok(self.rnn[i + 1])
+                # (not under dropout: the layer returns the sum and the dropped sum feeds the
+                # next quantiser, at the cost of the direction-sum launch)
+                pair = self.stack_fix and i + 1 < len(self.rnn) and RNN.pairs_ok(self.rnn[i + 1]) and not drop
                 out = RNN.recurrent_layer_hip(layer, inp, lens, i, pair_out=pair)
             else:
                 from ..utils import trace as TR
                 with TR.phase(TR.rnn_cell(i)):
                     out = layer.forward_ref(inp, lens)
             inp = out if self.stack_fix else x
+            if drop and i + 1 < len(self.rnn):
+                inp = self._drop(out, i)
         self._tap("rnn", out)
         return out
 

@@ -483,3 +483,60 @@ def specaug_mean_ref(x: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
             acc = acc[0::2] + acc[1::2]
         out[b] = acc[0] / np.float32(L)
     return torch.from_numpy(out)
+
+
+# ---- dropout between recurrent layers (ops/dropout.py, csrc/dropout.hip) ------------------
+def seq_dropout_threshold(p: float) -> int:
+    """thr = clamp(round(p * 65536), 0, 65535) of a drop probability p in [0, 1): the effective
+    probability is exactly thr / 65536, and thr == 0 is no dropout at all."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout probability must lie in [0, 1), not %r" % (p,))
+    return min(max(int(round(p * 65536)), 0), 65535)
+
+
+def seq_dropout_scale(thr: int) -> float:
+    """65536 / (65536 - thr) as one correctly rounded fp32 division."""
+    return float(np.float32(65536) / np.float32(65536 - int(thr)))
+
+
+def seq_dropout_mask_ref(T: int, N: int, H: int, seed: int, step: int, first_utt: int, site: int, thr: int,
+                         locked: bool) -> torch.Tensor:
+    """The keep mask, bool [T, N, H] (True: kept), of the dropout between recurrent layers, in
+    exact integer arithmetic. Element (t, b, i) has group g = i >> 3 and slot e = i & 7; the
+    Philox4x32-10 block of key seed and counter (locked ? 0 : t, first_utt + b, step,
+    0x80000000 | locked << 30 | site << 16 | g) gives words x0..x3, r = (x[e >> 1] >> (16 * (e & 1)))
+    & 0xffff, and the element is kept iff r >= thr. Any H: a last partial group uses its first
+    slots."""
+    site, thr, locked = int(site), int(thr), bool(locked)
+    G = (H + 7) // 8
+    if not (0 <= site < 16384 and G <= 65536 and 0 <= thr <= 65535):
+        raise ValueError("seq_dropout: site < 16384, H <= 8 * 65536, thr in [0, 65535]")
+    Tm = 1 if locked else T
+    t = np.arange(Tm, dtype=np.uint64)[:, None, None]
+    u = ((int(first_utt) + np.arange(N, dtype=np.uint64)) & np.uint64(0xffffffff))[None, :, None]
+    c3 = np.uint64(0x80000000 | (int(locked) << 30) | (site << 16)) | np.arange(G, dtype=np.uint64)[None, None, :]
+    key = (np.uint64(seed & 0xffffffff), np.uint64((seed >> 32) & 0xffffffff))
+    words = philox4x32((t, u, np.uint64(step & 0xffffffff), c3), key)
+    r = np.empty((Tm, N, G, 8), np.uint64)
+    for j, w in enumerate(words):
+        w = np.broadcast_to(w, (Tm, N, G))
+        r[..., 2 * j] = w & np.uint64(0xffff)
+        r[..., 2 * j + 1] = (w >> np.uint64(16)) & np.uint64(0xffff)
+    keep = (r >= np.uint64(thr)).reshape(Tm, N, G * 8)[:, :, :H]
+    return torch.from_numpy(np.array(np.broadcast_to(keep, (T, N, H))))
+
+
+def seq_dropout_ref(x: torch.Tensor, seed: int, step: int, first_utt: int, site: int, thr: int,
+                    locked: bool) -> torch.Tensor:
+    """Dropout of x [T, N, H] under seq_dropout_mask_ref, on x's device: a kept element gives
+    bf16(float(x) * scale) for a bf16 x (x * scale in x's precision otherwise) with scale =
+    fp32(65536) / fp32(65536 - thr), a dropped one +0 by selection, whatever the input holds
+    there. thr == 0: x itself. Differentiable: the gradient is the same map of the incoming one."""
+    if int(thr) == 0:
+        return x
+    T, N, H = x.shape
+    keep = seq_dropout_mask_ref(T, N, H, seed, step, first_utt, site, thr, locked).to(x.device)
+    scale = seq_dropout_scale(thr)
+    y = (x.float() * scale).to(x.dtype) if x.dtype in (torch.bfloat16, torch.float16) else x * scale
+    return torch.where(keep, y, torch.zeros((), dtype=x.dtype, device=x.device))

@@ -177,7 +177,11 @@ def main(argv=None) -> int:
         print("Running on platform: ", args.platform)
     ctx.barrier()
 
-    model = DeepSpeech2(**C.model_kwargs_from_args(args)).to(dev)
+    # --rnn_dropout: a training hyper-parameter like --specaug (masks per seed, global step and
+    # global utterance index), so it is not part of the architecture evaluation rebuilds
+    model = DeepSpeech2(**C.model_kwargs_from_args(args), rnn_dropout=args.rnn_dropout,
+                        rnn_dropout_mode=args.rnn_dropout_mode).to(dev)
+    model.rnn_dropout_seed = args.seed
     model.set_engine(engine, dtype, fp8=(args.dtype == "fp8" and engine == "hip"))
     # --engine mkldnn_rnn / cudnn_rnn (reference: MkldnnRNNCell, src/deepSpeech_NCHW.py:173-176)
     # checkpoints keep the MKL-DNN single-blob RNN parameters (utils/mkldnn_blob.py)
@@ -189,6 +193,9 @@ def main(argv=None) -> int:
                       allreduce_bf16=args.allreduce_dtype == "bf16", nan_policy=args.nan_policy,
                       step_graphs={"auto": "auto", "on": True, "off": False}[args.step_graphs],
                       defer_update=True, dp_graphs=args.dp_step_graphs)
+    trainer.first_utt = ctx.rank * args.batch_size
+    if ctx.is_main and model.rnn_dropout_thr > 0:
+        print("rnn_dropout:  p=%g (%d/65536), %s" % (args.rnn_dropout, model.rnn_dropout_thr, args.rnn_dropout_mode))
     # --specaug: masks and warp drawn per (seed, global step, global utterance index), so a
     # resumed run and any world size see the masks of the uninterrupted single-process run
     aug = None
@@ -241,7 +248,7 @@ def main(argv=None) -> int:
             hb_ = data.next()
             return collapse_batch_labels(hb_) if args.ctc_collapse_repeated else hb_
     src = _Src()
-    if aug is not None and args.dummy and start > 0:
+    if (aug is not None or model.rnn_dropout_thr > 0) and args.dummy and start > 0:
         # an augmented synthetic run resumes its feed too (the generators are cheap to replay), so
         # its steps are those of the uninterrupted run: the same batch under the same masks
         for _ in range(start):

@@ -161,6 +161,9 @@ class Trainer:
         # (per arena: another Trainer / model in this process keeps its own setting)
         self.arena.wgrad.set_deferral(world_size == 1 and not self.bucketer.enabled)
         self.global_step = 0
+        # global index of this rank's first utterance (rank * batch size): with the global step it
+        # selects the dropout masks of a model with rnn_dropout (ops/dropout.py)
+        self.first_utt = 0
         self.nan_policy = nan_policy
         self.collapse_repeated = collapse_repeated
         self.loss_ema: Optional[float] = None
@@ -319,6 +322,11 @@ class Trainer:
         # one Adam step count / EMA decay per training step, on the host, whatever runs it
         lr_t, keep = self.opt.prepare(self.lr, self.global_step)
         self.arena.ensure_bf16()      # outside any graph: a restore / EMA swap marks it dirty
+        drop = getattr(self.model, "dropout_state", None)
+        if drop is not None:
+            # the step and utterance offset the dropout masks are drawn for, on the device: the
+            # kernels read them, so the eager body and a replayed graph see this step's masks
+            drop.set(self.global_step, self.first_utt)
         if self.graphs_active():
             loss = self._graph_step(batch, lr_t, keep)
         else:
