@@ -345,9 +345,10 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmArgs g) {
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
       const uint2 b2 = braw[j];
-      const float on = has_bias ? 1.f : 0.f;
-      bv[j][0] = on * bf2f((bf16_t)(b2.x & 0xffff)); bv[j][1] = on * bf2f((bf16_t)(b2.x >> 16));
-      bv[j][2] = on * bf2f((bf16_t)(b2.y & 0xffff)); bv[j][3] = on * bf2f((bf16_t)(b2.y >> 16));
+      // without a bias the load above read B's memory, which may hold anything (the gap of a
+      // row-stride view, a NaN or an infinity): selected away, never multiplied by zero
+      bv[j][0] = has_bias ? bf2f((bf16_t)(b2.x & 0xffff)) : 0.f; bv[j][1] = has_bias ? bf2f((bf16_t)(b2.x >> 16)) : 0.f;
+      bv[j][2] = has_bias ? bf2f((bf16_t)(b2.y & 0xffff)) : 0.f; bv[j][3] = has_bias ? bf2f((bf16_t)(b2.y >> 16)) : 0.f;
     }
     if constexpr (PERS) {
       const int nid = id + id_step;

@@ -627,6 +627,8 @@ int fill_prob(G8Prob& p, const void* A, const void* B, void* C, float* ws, unsig
   if ((a_col && M % 8) || (b_col && N % 8)) return (int)hipErrorInvalidValue;
   if (((lda * es) % 16) || ((ldb * es) % 16) || ((uintptr_t)A % 16) || ((uintptr_t)B % 16))
     return (int)hipErrorInvalidValue;
+  // the epilogue and g8_reduce_kernel store 8-B (bf16) / 16-B (fp32) vectors at m * ldc + n
+  if (ldc % 4 != 0) return (int)hipErrorInvalidValue;
   // 32-bit buffer offsets: each operand under 2 GB, a split's workspace too
   if ((long long)(a_col ? K : M) * lda * es >= (1LL << 31) || (long long)(b_col ? K : N) * ldb * es >= (1LL << 31))
     return (int)hipErrorInvalidValue;
