@@ -8,8 +8,10 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "api.h"
@@ -479,15 +481,46 @@ void bn_bwd(at::Tensor dout, at::Tensor y, at::Tensor mean, at::Tensor invstd, a
 }
 
 // --------------------------------------------------------------------------- optimizer
+// What the Adam + EMA kernels assume of their arrays (csrc/optim.hip: f32x4 accesses of the fp32
+// arrays, uint2 stores of the bf16 copy): n elements each, contiguous, fp32 16-B and bf16 8-B aligned
+static void adam_arrays_check(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const at::Tensor& v,
+                              const OptT& ema, const OptT& p16, const OptT& hyper, const char* what) {
+  const int64_t n = p.numel();
+  const at::Tensor* f32s[4] = {&p, &g, &m, &v};
+  const char* names[4] = {"p", "g", "m", "v"};
+  for (int i = 0; i < 4; ++i) {
+    need_gpu(*f32s[i], names[i]);
+    TORCH_CHECK(f32s[i]->scalar_type() == at::kFloat, what, ": fp32 arena expected (", names[i], ")");
+    TORCH_CHECK(f32s[i]->numel() == n, what, ": arena size mismatch (", names[i], ")");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(f32s[i]->data_ptr()) % 16 == 0, what, ": ", names[i],
+                " must be 16-byte aligned");
+  }
+  if (ema.has_value() && ema->defined()) {
+    need_gpu(*ema, "ema");
+    TORCH_CHECK(ema->scalar_type() == at::kFloat && ema->numel() == n, what, ": ema must be fp32 of p's size");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(ema->data_ptr()) % 16 == 0, what, ": ema must be 16-byte aligned");
+  }
+  if (p16.has_value() && p16->defined()) {
+    need_gpu(*p16, "p16");
+    TORCH_CHECK(p16->scalar_type() == at::kBFloat16 && p16->numel() == n, what, ": p16 must be bf16 of p's size");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(p16->data_ptr()) % 8 == 0, what, ": p16 must be 8-byte aligned");
+  }
+  if (hyper.has_value() && hyper->defined()) {
+    need_gpu(*hyper, "hyper");
+    TORCH_CHECK(hyper->scalar_type() == at::kFloat && hyper->numel() >= 2, what, ": hyper must be fp32 {lr_t, ema_keep}");
+  }
+}
+
 void adam_ema(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, OptT ema, OptT p16, double lr_t, double b1,
               double b2, double eps, double gscale, double ema_keep, OptT skip, int64_t max_grid, OptT hyper,
               int64_t lds_reserve) {
-  need_gpu(p, "p");
   TORCH_CHECK(lds_reserve >= 0 && lds_reserve <= 65536, "adam_ema: lds_reserve in [0, 64 KB]");
-  need_gpu(g, "g");
-  TORCH_CHECK(p.scalar_type() == at::kFloat && g.scalar_type() == at::kFloat, "fp32 arena expected");
+  adam_arrays_check(p, g, m, v, ema, p16, hyper, "adam_ema");
+  if (skip.has_value() && skip->defined()) {
+    need_gpu(*skip, "skip");
+    TORCH_CHECK(skip->scalar_type() == at::kInt && skip->numel() >= 1, "adam_ema: skip must be an int32 flag");
+  }
   const long long n = p.numel();
-  TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n, "arena size mismatch");
   check(ds2_adam_ema(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
                      ptr_or_null<float>(ema, "ema"), ptr_or_null<void>(p16, "p16"), n, (float)lr_t, (float)b1,
                      (float)b2, (float)eps, (float)gscale, (float)ema_keep, ptr_or_null<const int>(skip, "skip"),
@@ -499,13 +532,17 @@ void adam_ema(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, OptT ema, 
 void adam_ema_ranges(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, OptT ema, OptT p16,
                      std::vector<int64_t> lohi, double lr_t, double b1, double b2, double eps, double gscale,
                      double ema_keep, OptT hyper) {
-  need_gpu(p, "p");
-  need_gpu(g, "g");
-  TORCH_CHECK(p.scalar_type() == at::kFloat && g.scalar_type() == at::kFloat, "fp32 arena expected");
+  adam_arrays_check(p, g, m, v, ema, p16, hyper, "adam_ema_ranges");
   const long long n = p.numel();
-  TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n, "arena size mismatch");
   TORCH_CHECK(lohi.size() % 2 == 0, "adam_ema_ranges: (lo, hi) pairs");
   for (size_t i = 0; i < lohi.size(); ++i) TORCH_CHECK(lohi[i] >= 0 && lohi[i] <= n, "adam_ema_ranges: range");
+  // two ranges sharing an element would be updated by two threads at once
+  std::vector<std::pair<int64_t, int64_t>> sorted;
+  for (size_t i = 0; i + 1 < lohi.size(); i += 2)
+    if (lohi[i + 1] > lohi[i]) sorted.emplace_back(lohi[i], lohi[i + 1]);
+  std::sort(sorted.begin(), sorted.end());
+  for (size_t i = 1; i < sorted.size(); ++i)
+    TORCH_CHECK(sorted[i].first >= sorted[i - 1].second, "adam_ema_ranges: ranges overlap");
   std::vector<long long> r(lohi.begin(), lohi.end());
   check(ds2_adam_ema_ranges(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
                             ptr_or_null<float>(ema, "ema"), ptr_or_null<void>(p16, "p16"), r.data(),
@@ -518,6 +555,11 @@ int64_t grad_norm_blocks(int64_t n) { return ds2_grad_norm_blocks(n); }
 
 void grad_norm(at::Tensor g, double gscale, at::Tensor part, at::Tensor bad) {
   need_gpu(g, "g");
+  need_gpu(part, "part");
+  need_gpu(bad, "bad");
+  TORCH_CHECK(g.scalar_type() == at::kFloat, "grad_norm: fp32 gradients");
+  TORCH_CHECK(part.scalar_type() == at::kFloat && part.numel() >= 1, "grad_norm: part must be a non-empty fp32 tensor");
+  TORCH_CHECK(bad.scalar_type() == at::kInt && bad.numel() == 1, "grad_norm: bad must be one int32");
   check(ds2_grad_norm(g.data_ptr<float>(), g.numel(), (float)gscale, part.data_ptr<float>(), (int)part.numel(),
                       bad.data_ptr<int>(), cur_stream()),
         "grad_norm");
@@ -685,8 +727,8 @@ void ctc_greedy(at::Tensor logits, at::Tensor lens, at::Tensor labels, at::Tenso
 // fill each (contiguous tensor, 32-bit pattern) region in ONE launch (<= 8 regions)
 // out [C, R] = in [R, C]^T (bf16, unit-stride rows)
 void transpose_bf16(at::Tensor in, at::Tensor out) {
-  need_gpu(in, "in");
-  need_gpu(out, "out");
+  // rows may be pitched (row stride > row length): the kernel takes both row strides
+  TORCH_CHECK(in.is_cuda() && out.is_cuda(), "transpose_bf16: GPU tensors");
   TORCH_CHECK(in.scalar_type() == at::kBFloat16 && out.scalar_type() == at::kBFloat16, "transpose_bf16: bf16");
   TORCH_CHECK(in.dim() == 2 && out.dim() == 2 && in.stride(1) == 1 && out.stride(1) == 1, "transpose_bf16: 2-D rows");
   TORCH_CHECK(out.size(0) == in.size(1) && out.size(1) == in.size(0), "transpose_bf16: out must be [C, R]");
@@ -707,8 +749,8 @@ void multi_copy(std::vector<at::Tensor> dsts, std::vector<at::Tensor> srcs, c10:
   unsigned srow[8], drow[8], spitch[8], dpitch[8];
   for (size_t i = 0; i < dsts.size(); ++i) {
     at::Tensor d = dsts[i], s = srcs[i];
-    need_gpu(d, "multi_copy dst");
-    need_gpu(s, "multi_copy src");
+    // 2-D pairs may be pitched views (unit-stride rows, checked below); 1-D ones are contiguous
+    TORCH_CHECK(d.is_cuda() && s.is_cuda(), "multi_copy: GPU tensors");
     TORCH_CHECK(d.scalar_type() == s.scalar_type() && d.dim() == s.dim() && (d.dim() == 1 || d.dim() == 2),
                 "multi_copy: same dtype, 1-D or 2-D");
     const int64_t es = d.element_size();
@@ -720,6 +762,8 @@ void multi_copy(std::vector<at::Tensor> dsts, std::vector<at::Tensor> srcs, c10:
     } else {
       TORCH_CHECK(d.size(0) == s.size(0) && s.size(1) <= d.size(1) && d.stride(1) == 1 && s.stride(1) == 1,
                   "multi_copy: rows match, unit-stride rows, src cols <= dst cols");
+      TORCH_CHECK((d.size(0) <= 1 || d.stride(0) >= d.size(1)) && (s.size(0) <= 1 || s.stride(0) >= s.size(1)),
+                  "multi_copy: rows must not overlap");
       rows[i] = (unsigned long long)d.size(0);
       srow[i] = (unsigned)(s.size(1) * es); drow[i] = (unsigned)(d.size(1) * es);
       spitch[i] = (unsigned)(std::max<int64_t>(s.stride(0), s.size(1)) * es);
@@ -949,7 +993,9 @@ void fc_bias_grad(at::Tensor G, int64_t K, at::Tensor scale, double alpha, at::T
   need_gpu(scale, "scale");
   need_gpu(out, "out");
   TORCH_CHECK(G.dim() == 2 && G.scalar_type() == at::kBFloat16 && G.stride(1) == 1, "fc_bias_grad: G bf16 [M, ldg]");
-  TORCH_CHECK(K >= 1 && K <= 32 && G.size(1) >= 32 && G.stride(0) % 8 == 0 && G.data_ptr<at::BFloat16>() != nullptr &&
+  // M = 0 (an empty tensor has no data pointer) is legal: out = 0, or out unchanged under acc
+  TORCH_CHECK(K >= 1 && K <= 32 && G.size(1) >= 32 && G.stride(0) % 8 == 0 &&
+                  (G.size(0) == 0 || G.data_ptr<at::BFloat16>() != nullptr) &&
                   reinterpret_cast<uintptr_t>(G.data_ptr()) % 16 == 0,
               "fc_bias_grad: 1 <= K <= 32, G of >= 32 columns, row stride % 8 == 0, 16-B aligned");
   TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.numel() >= 1, "fc_bias_grad: fp32 device scale");
@@ -996,6 +1042,9 @@ void fp8_quant2(at::Tensor a, at::Tensor b, double alpha, at::Tensor a8, at::Ten
   TORCH_CHECK(scales.scalar_type() == at::kFloat && scales.numel() >= 2, "scales: 2 floats");
   TORCH_CHECK((reinterpret_cast<uintptr_t>(a.data_ptr()) & 15) == 0 && (reinterpret_cast<uintptr_t>(b.data_ptr()) & 15) == 0,
               "16-B aligned operands expected");
+  // the cast stores 8 bytes (uint2) per chunk
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(a8.data_ptr()) & 7) == 0 && (reinterpret_cast<uintptr_t>(b8.data_ptr()) & 7) == 0,
+              "fp8_quant2: a8 / b8 must be 8-byte aligned");
   const int nb = ds2_fp8_quant_blocks(a.size(0) * Kp, b.size(0) * Kp);
   TORCH_CHECK(part.scalar_type() == at::kFloat && part.numel() >= 2 * nb, "part: 2*blocks floats");
   check(ds2_fp8_quant2(a.data_ptr(), a.size(0), b.data_ptr(), b.size(0), (int)K, (int)Kp, (float)alpha, a8.data_ptr(),

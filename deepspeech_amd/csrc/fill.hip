@@ -2,6 +2,8 @@
 // kernels (exchange sentinels, census words, error word, initial state slot, bias-gradient
 // partials): up to 8 (pointer, bytes, 32-bit pattern) regions filled by one grid instead of
 // one torch fill kernel (~5 us of launch + tail each on the critical path) per region.
+#include <algorithm>
+
 #include "common.h"
 
 using namespace ds2;
@@ -191,7 +193,11 @@ __global__ __launch_bounds__(256) void prep_inputs_kernel(const float* __restric
 extern "C" int ds2_prep_inputs(const float* x, void* y, long long n, const int* lens_in, int* lens_out, int nl,
                                hipStream_t st) {
   if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(y) & 7)) return -52;
-  long long blocks = (n / 4 + 255) / 256;
+  // the lengths are written one per thread (no loop): the grid covers max(n / 4, nl) threads,
+  // and more lengths than the capped grid holds are refused
+  if (nl < 0 || nl > 2048 * 256) return -53;
+  const long long work = std::max<long long>(n / 4, nl);
+  long long blocks = (work + 255) / 256;
   if (blocks < 1) blocks = 1;
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(prep_inputs_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, (bf16_t*)y, n, lens_in,

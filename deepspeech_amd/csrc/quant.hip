@@ -85,9 +85,13 @@ __global__ __launch_bounds__(QT) void amax2_kernel(const bf16_t* __restrict__ a,
   if (threadIdx.x == 0) part[blockIdx.x] = m;
 }
 
+// Saturating cast. fmaxf / fminf drop a NaN operand (the clamp alone would store NaN as -448, a
+// finite value that dequantises to -amax), so the NaN byte is selected back in afterwards: a NaN
+// element, or inf * 0 under an infinite amax, reaches the GEMM and the non-finite watch as NaN.
 __device__ __forceinline__ unsigned char to_e4m3(float f) {
   const __hip_fp8_e4m3 q(fminf(fmaxf(f, -FP8_MAX), FP8_MAX));
-  return *reinterpret_cast<const unsigned char*>(&q);
+  const unsigned char b = *reinterpret_cast<const unsigned char*>(&q);
+  return f != f ? (unsigned char)0x7F : b;
 }
 
 // Casts [rows][K] bf16 to [rows][Kp] e4m3 (Kp >= K, K % 8 == 0): the padding columns are
