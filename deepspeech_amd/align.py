@@ -142,6 +142,7 @@ class Aligner:
         self.dev = model.fc_weight.device
         self.features = features
         self._featurizer = None
+        self._featurizer_key = None
 
     @torch.no_grad()
     def align(self, feats: torch.Tensor, seq_lens: torch.Tensor, transcripts, durations=None
@@ -164,12 +165,20 @@ class Aligner:
         return utterances(al, ids, lens, durations)
 
     @torch.no_grad()
-    def align_audio(self, pcm, transcripts, sample_rate: int = 16000) -> List[UtteranceAlignment]:
+    def align_audio(self, pcm, transcripts, sample_rate: int = 16000,
+                    resample: bool = False) -> List[UtteranceAlignment]:
         """pcm: [B, S] samples or a list of 1-D arrays (int16 or float), featurized on the model's
-        device (ops/featurize.py AudioFeaturizer)."""
-        if self._featurizer is None or self._featurizer.sample_rate != sample_rate:
+        device (ops/featurize.py AudioFeaturizer). ``resample=True`` converts ``sample_rate`` to
+        16 kHz on the device first (ops/resample.py) instead of featurizing at ``sample_rate``;
+        durations come from the original sample counts either way."""
+        key = (int(sample_rate), bool(resample))
+        if self._featurizer is None or self._featurizer_key != key:
             from .ops.featurize import AudioFeaturizer
-            self._featurizer = AudioFeaturizer(self.features, sample_rate=sample_rate, device=self.dev)
+            if resample:
+                self._featurizer = AudioFeaturizer(self.features, device=self.dev, input_rate=sample_rate)
+            else:
+                self._featurizer = AudioFeaturizer(self.features, sample_rate=sample_rate, device=self.dev)
+            self._featurizer_key = key
         if isinstance(pcm, (torch.Tensor, np.ndarray)) and getattr(pcm, "ndim", 1) == 2:
             samples = [int(pcm.shape[1])] * int(pcm.shape[0])
         else:

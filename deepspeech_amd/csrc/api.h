@@ -349,4 +349,16 @@ int ds2_audio_stats(const void* pcm, int in_i16, long long row_stride, int S, in
                     float* gain, hipStream_t st);
 int ds2_featurize(const DS2Feat* a, int kind, int in_i16, int out_bf16, hipStream_t st);
 
+// ---- resample.hip ------------------------------------------------------------------------
+// Polyphase resampling of PCM rows: x fp32 / int16 [B, S] (rows row_stride samples apart), lens
+// [B] valid samples or null, h fp32 [L, K] (K even, K <= 320, L * K <= 24576), out fp32
+// [B, n_out], out_lens int32 [B]. Output j reads x[in_off + (ph0 + j M) / L + k], k < K, with
+// phase (ph0 + j M) % L; to_end: a row's outputs stop with its samples (else every row has
+// n_out). -90: shape outside the contract, -91: in_off / ph0 outside their ranges.
+int ds2_resample_tile();
+int ds2_resample_supported(int L, int M, int K);
+int ds2_resample(const void* x, int in_i16, long long row_stride, int S, int B, const int* lens, const float* h,
+                 int L, int M, int K, int in_off, int ph0, int n_out, int to_end, float* out, int* out_lens,
+                 hipStream_t st);
+
 }  // extern "C"

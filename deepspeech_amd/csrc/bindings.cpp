@@ -1529,6 +1529,30 @@ void featurize(at::Tensor pcm, OptT lens, at::Tensor offset, at::Tensor gain, at
   check(ds2_featurize(&a, (int)kind, i16, is_bf16(out), cur_stream()), "featurize");
 }
 
+// --------------------------------------------------------------------------- resampling (csrc/resample.hip)
+// out [B, n_out] fp32 and out_lens [B] int32 of one whole call (in_off = -(K/2 - 1), ph0 = 0, to_end) or of one
+// stream push (buffer-relative in_off and start phase)
+void resample(at::Tensor pcm, OptT lens, at::Tensor h, int64_t L, int64_t M, int64_t in_off, int64_t ph0,
+              bool to_end, at::Tensor out, at::Tensor out_lens) {
+  const int i16 = pcm_is_i16(pcm);
+  const int64_t B = pcm.size(0), S = pcm.size(1);
+  TORCH_CHECK(pcm.is_contiguous() && S < (1LL << 31), "resample: pcm must be contiguous [B, S], S < 2^31");
+  for (const at::Tensor* t : {&h, &out, &out_lens}) need_gpu(*t, "resample operand");
+  TORCH_CHECK(h.scalar_type() == at::kFloat && h.dim() == 2 && h.is_contiguous() && h.size(0) == L,
+              "resample: h must be contiguous fp32 [L, K]");
+  const int64_t K = h.size(1);
+  TORCH_CHECK(L >= 1 && M >= 1 && ds2_resample_supported((int)L, (int)M, (int)K),
+              "resample: (L, M, K) outside the kernel's contract");
+  TORCH_CHECK(out.scalar_type() == at::kFloat && out.dim() == 2 && out.size(0) == B && out.is_contiguous() &&
+                  out.size(1) < (1LL << 31), "resample: out must be contiguous fp32 [B, n_out]");
+  TORCH_CHECK(out_lens.scalar_type() == at::kInt && out_lens.numel() == B, "resample: out_lens must be int32 [B]");
+  TORCH_CHECK(in_off > -(1LL << 31) && in_off < (1LL << 31) && ph0 >= 0 && ph0 < L, "resample: in_off / ph0");
+  check(ds2_resample(pcm.data_ptr(), i16, S, (int)S, (int)B, feat_lens(lens, B), h.data_ptr<float>(), (int)L, (int)M,
+                     (int)K, (int)in_off, (int)ph0, (int)out.size(1), to_end ? 1 : 0, out.data_ptr<float>(),
+                     out_lens.data_ptr<int>(), cur_stream()),
+        "resample");
+}
+
 // --------------------------------------------------------------------------- summaries (csrc/stats.hip)
 void hist_stats(at::Tensor x, at::Tensor counts, at::Tensor part) {
   need_gpu(x, "x");
@@ -1698,6 +1722,12 @@ PYBIND11_MODULE(_C, m) {
   m.def("featurize", &featurize, py::arg("pcm"), py::arg("lens"), py::arg("offset"), py::arg("gain"),
         py::arg("basis"), py::arg("mel_idx"), py::arg("mel_w"), py::arg("dct"), py::arg("lifter"), py::arg("kind"),
         py::arg("lead"), py::arg("mode"), py::arg("out"), py::arg("frames"));
+  m.def("resample", &resample, py::arg("pcm"), py::arg("lens"), py::arg("h"), py::arg("L"), py::arg("M"),
+        py::arg("in_off"), py::arg("ph0"), py::arg("to_end"), py::arg("out"), py::arg("out_lens"));
+  m.def("resample_tile", []() { return ds2_resample_tile(); });
+  m.def("resample_supported", [](int64_t L, int64_t M, int64_t K) {
+    return ds2_resample_supported((int)L, (int)M, (int)K) != 0;
+  });
   m.def("hist_stats", &hist_stats);
   m.def("hist_nbucket", []() { return ds2_hist_nbucket(); });
   m.def("hist_blocks", [](int64_t n) { return ds2_hist_blocks(n); });

@@ -2,11 +2,14 @@
 
   python -m deepspeech_amd.data.preprocess --audio_path ../data/LibriSpeech/audio \
          --out_dir ../data/LibriSpeech/processed [--features mfcc|spectrogram] [--tfrecords]
-         [--featurizer numpy|gpu]
+         [--featurizer numpy|gpu] [--resample_to RATE]
 
 ``--featurizer numpy`` (default) runs data/featurizer.py one file at a time; ``gpu`` batches
 about 64 utterances per call through the HIP featurizer (ops/featurize.py) and feeds the same
-sort / store / TFRecord code.
+sort / store / TFRecord code. ``--resample_to RATE`` (0: off) converts every file whose rate is
+not RATE to it before featurizing: with ``numpy`` through the fp64 oracle
+(ops/reference.py resample_ref), with ``gpu`` on the device (ops/resample.py); off, a file is
+featurized at its own rate.
 
 For every partition directory under ``audio_path`` (train-clean-100, dev-clean, ...):
 read ``*.trans.txt`` transcripts, decode audio, compute features, map characters with the
@@ -81,7 +84,7 @@ def scan_partition(part_dir: str) -> List[Tuple[str, str]]:
 GPU_GROUP = 64        # utterances per AudioFeaturizer call of --featurizer gpu
 
 
-def _gpu_features(items: List[Tuple[str, str]], features: str) -> list:
+def _gpu_features(items: List[Tuple[str, str]], features: str, resample_to: int = 0) -> list:
     """[(feats, labels, text)] in the order of ``items``, featurized on the GPU in groups of
     GPU_GROUP files sorted by length (bounds the padding of a group's [B, S_max] upload)."""
     import torch
@@ -100,7 +103,11 @@ def _gpu_features(items: List[Tuple[str, str]], features: str) -> list:
         for sr in sorted({g[1] for g in group}):
             idx = [i for i in order if group[i][1] == sr]
             if sr not in fz:
-                fz[sr] = AudioFeaturizer(features, sample_rate=sr, device="cuda", normalize="utterance")
+                if resample_to:
+                    fz[sr] = AudioFeaturizer(features, sample_rate=resample_to, device="cuda",
+                                             normalize="utterance", input_rate=sr)
+                else:
+                    fz[sr] = AudioFeaturizer(features, sample_rate=sr, device="cuda", normalize="utterance")
             # float32 PCM on the device: exact for 16-bit audio
             feats, frames = fz[sr]([group[i][0].astype(np.float32) for i in idx])
             feats, frames = feats.cpu().numpy(), frames.cpu().tolist()
@@ -113,15 +120,19 @@ def _gpu_features(items: List[Tuple[str, str]], features: str) -> list:
 
 def process_partition(part_dir: str, out_prefix: str, features: str = "mfcc",
                       tfrecord_dir: str = "", is_train: bool = False, min_bin: int = 20,
-                      featurizer: str = "numpy") -> Dict[str, int]:
+                      featurizer: str = "numpy", resample_to: int = 0) -> Dict[str, int]:
     if featurizer not in ("numpy", "gpu"):
         raise ValueError("featurizer must be 'numpy' or 'gpu', not %r" % (featurizer,))
+    resample_to = int(resample_to)
     utts = []
     if featurizer == "gpu":
-        utts = _gpu_features(scan_partition(part_dir), features)
+        utts = _gpu_features(scan_partition(part_dir), features, resample_to)
     else:
         for path, text in scan_partition(part_dir):
             audio, sr = read_audio(path)
+            if resample_to and sr != resample_to:
+                from ..ops.reference import resample_ref
+                audio, sr = resample_ref(audio, sr, resample_to), resample_to
             feats = compute_features(audio, sr, features)
             utts.append((feats, encode_transcript(text), text))
     utts.sort(key=lambda u: u[0].shape[0])                 # SortaGrad order
@@ -156,6 +167,8 @@ def main(argv=None):
     ap.add_argument("--tfrecords", action="store_true")
     ap.add_argument("--featurizer", default="numpy", choices=["numpy", "gpu"],
                     help="numpy: data/featurizer.py, one file at a time; gpu: batched HIP kernels (ops/featurize.py)")
+    ap.add_argument("--resample_to", type=int, default=0, metavar="RATE",
+                    help="resample every file to RATE Hz before featurizing (0: featurize at the file's rate)")
     a = ap.parse_args(argv)
     for part in sorted(glob.glob(os.path.join(a.audio_path, "*"))):
         if not os.path.isdir(part):
@@ -163,7 +176,7 @@ def main(argv=None):
         name = os.path.basename(part)
         stats = process_partition(part, os.path.join(a.out_dir, name), a.features,
                                   a.out_dir if a.tfrecords else "", is_train=name.startswith("train"),
-                                  featurizer=a.featurizer)
+                                  featurizer=a.featurizer, resample_to=a.resample_to)
         print(name, stats)
 
 

@@ -54,15 +54,18 @@ def frames_out(T: int) -> int:
 class StreamingRecognizer:
     def __init__(self, model: DeepSpeech2, decoder: str = "greedy", beam_width: int = 16, batch: int = 1,
                  graphs: Optional[bool] = None, features: str = "mfcc", audio_gain: Optional[float] = None,
-                 lm=None, lm_weight: float = 1.0, label_bonus: float = 0.0):
+                 lm=None, lm_weight: float = 1.0, label_bonus: float = 0.0, audio_rate: int = 16000):
         """``lm`` (a deepspeech_amd.lm.CharNgramLM, beam decoder only): shallow fusion with weight
-        ``lm_weight`` and a per-label bonus ``label_bonus`` (ops/decode.py)."""
+        ``lm_weight`` and a per-label bonus ``label_bonus`` (ops/decode.py). ``audio_rate``: the
+        sample rate of the PCM given to accept_audio(); other than 16 kHz it is resampled on the
+        device first (ops/resample.py), which delays the audio by half the filter's taps."""
         if model.bidirectional:
             raise ValueError("streaming needs a unidirectional model (rnn_type='uni-dir')")
         # accept_audio(): PCM is featurized on the model's device (ops/featurize.py) with a fixed
         # gain (None: 1/32768 for int16 PCM, 1 for float); the featurizer is built on first use
         self.features = features
         self.audio_gain = audio_gain
+        self.audio_rate = int(audio_rate)
         self._featurizer = None
         self._audio = None
         self.model = model.eval()
@@ -124,14 +127,15 @@ class StreamingRecognizer:
 
     @torch.no_grad()
     def accept_audio(self, pcm, final: bool = False) -> List[List[int]]:
-        """Feed [B, S_c] PCM samples (int16 or float, 16 kHz); the feature frames they complete go
+        """Feed [B, S_c] PCM samples (int16 or float, at ``audio_rate``, 16 kHz unless the
+        recognizer was built with another); the feature frames they complete go
         through accept(). ``final=True`` also emits the zero-padded last frame. Returns the newly
         decoded (greedy) labels per stream."""
         t0 = time.perf_counter()
         if self._featurizer is None:
             from .ops.featurize import AudioFeaturizer
             self._featurizer = AudioFeaturizer(self.features, device=self.dev, normalize="fixed",
-                                               gain=self.audio_gain)
+                                               gain=self.audio_gain, input_rate=self.audio_rate)
             self._audio = self._featurizer.stream(self.B)
         feats = self._audio.push(pcm, final=final)
         # no sync here: the kernels run ahead of accept()'s on the same stream, so their GPU time
@@ -352,18 +356,20 @@ class StreamingRecognizer:
 
 def rtf(model: DeepSpeech2, seconds: float = 10.0, chunk_s: float = 1.0, batch: int = 1,
         decoder: str = "greedy", beam_width: int = 16, seed: int = 0, audio: bool = False, lm=None,
-        lm_weight: float = 1.0, label_bonus: float = 0.0):
+        lm_weight: float = 1.0, label_bonus: float = 0.0, audio_rate: int = 16000):
     """Real-time factor of streaming synthetic audio: compute time / audio time (per stream;
     ``batch`` streams are processed together). Returns (rtf, transcripts). ``audio=True`` streams
     synthetic int16 PCM through accept_audio() (featurization included in the compute time)
-    instead of ready-made feature frames. ``lm``: a CharNgramLM fused into the beam decoder."""
+    instead of ready-made feature frames, sampled at ``audio_rate`` (other than 16 kHz: resampled
+    on the device, inside the compute time). ``lm``: a CharNgramLM fused into the beam decoder."""
     g = torch.Generator().manual_seed(seed)
     lmkw = {} if lm is None else dict(lm=lm, lm_weight=lm_weight, label_bonus=label_bonus)
     if audio:
-        n = int(round(seconds * 16000))
+        n = int(round(seconds * audio_rate))
         pcm = (torch.randn(batch, n, generator=g) * 3000.0).clamp_(-32768, 32767).to(torch.int16)
-        rec = StreamingRecognizer(model, decoder=decoder, beam_width=beam_width, batch=batch, **lmkw)
-        step = max(1, int(round(chunk_s * 16000)))
+        rec = StreamingRecognizer(model, decoder=decoder, beam_width=beam_width, batch=batch,
+                                  audio_rate=audio_rate, **lmkw)
+        step = max(1, int(round(chunk_s * audio_rate)))
         for s in range(0, n, step):
             rec.accept_audio(pcm[:, s:s + step], final=s + step >= n)
         res = rec.finish()

@@ -6,7 +6,8 @@ On a GPU at 16 kHz it runs the HIP kernels of ``csrc/featurize.hip`` (a missing 
 an error, never a silent fallback); on a CPU device, or at another sample rate, it computes
 with ``data/featurizer.py`` itself, so the interface works everywhere. That numpy module stays
 the fp64 oracle: every table the kernels consume is derived here from its formulas in fp64 and
-rounded to fp32 once.
+rounded to fp32 once. Audio recorded at another rate reaches the kernels through
+``input_rate``: it is resampled to ``sample_rate`` first (``ops/resample.py``), on the device.
 """
 from __future__ import annotations
 
@@ -17,6 +18,7 @@ import numpy as np
 import torch
 
 from ..data import featurizer as F
+from .resample import Resampler, pack_pcm
 
 HOP = 160                      # 10 ms at 16 kHz
 FRAME_LEN = {"mfcc": 400, "spectrogram": 320}
@@ -181,11 +183,18 @@ class AudioFeaturizer:
     normalisation per utterance, statistics computed on the device); ``normalize="fixed"``
     applies ``(x - offset) * gain`` with the given scalars (default gain 1/32768 for int16
     input, 1 for float).
+
+    ``input_rate`` (when given and different from ``sample_rate``) is the rate of the PCM handed
+    in: it is resampled ``input_rate -> sample_rate`` by ``ops/resample.py`` and then featurized,
+    on a GPU at 16 kHz as resample kernel, (statistics kernel,) featurize kernel with no
+    synchronisation between them. Utterance statistics are those of the resampled signal; the
+    default fixed gain still follows the dtype of the PCM handed in. Without it, a
+    ``sample_rate`` other than 16 kHz featurizes at that rate on the host.
     """
 
     def __init__(self, kind: str = "mfcc", sample_rate: int = 16000, device=None,
                  out_dtype: torch.dtype = torch.float32, normalize: str = "utterance",
-                 gain: Optional[float] = None, offset: float = 0.0):
+                 gain: Optional[float] = None, offset: float = 0.0, input_rate: Optional[int] = None):
         if kind not in FRAME_LEN:
             raise ValueError("kind must be 'mfcc' or 'spectrogram', not %r" % (kind,))
         if normalize not in ("utterance", "fixed"):
@@ -206,6 +215,10 @@ class AudioFeaturizer:
             from . import _ext
             self._C = _ext.ext()                     # raises if the extension is not built
             self._t = _tables(kind, self.sample_rate, self.device)
+        self.input_rate = None if input_rate is None else int(input_rate)
+        self._rs: Optional[Resampler] = None
+        if self.input_rate is not None and self.input_rate != self.sample_rate:
+            self._rs = Resampler(self.input_rate, self.sample_rate, self.device)
 
     # ---- helpers -------------------------------------------------------------------------
     def _gain_for(self, is_int16: bool) -> float:
@@ -217,28 +230,7 @@ class AudioFeaturizer:
         """-> (tensor [B, S] on the host or the device, lens or None). int16 stays int16; anything
         else becomes float32 for the kernels and float64 (exact) for the numpy path."""
         ft = torch.float32 if self.use_kernels else torch.float64
-        if isinstance(pcm, torch.Tensor) or (isinstance(pcm, np.ndarray) and pcm.ndim == 2):
-            t = pcm if isinstance(pcm, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pcm))
-            if t.dim() != 2:
-                raise ValueError("pcm must be [B, S] or a list of 1-D arrays")
-            if t.dtype != torch.int16:
-                t = t.to(ft)
-            if lens is not None:
-                lens = torch.as_tensor(lens, dtype=torch.int32)
-            return t, lens
-        if lens is not None:
-            raise ValueError("lens is implied by a list of utterances")
-        arrs = [u.detach().cpu().numpy() if isinstance(u, torch.Tensor) else np.asarray(u) for u in pcm]
-        if not arrs or any(a.ndim != 1 or a.size == 0 for a in arrs):
-            raise ValueError("pcm must be a non-empty list of non-empty 1-D arrays")
-        i16 = all(a.dtype == np.int16 for a in arrs)
-        B, S = len(arrs), max(a.size for a in arrs)
-        pin = self.use_kernels
-        buf = torch.zeros(B, S, dtype=torch.int16 if i16 else ft, pin_memory=pin)
-        view = buf.numpy()
-        for b, a in enumerate(arrs):
-            view[b, :a.size] = a
-        return buf, torch.tensor([a.size for a in arrs], dtype=torch.int32)
+        return pack_pcm(pcm, lens, ft, self.use_kernels)
 
     def _fixed_stats(self, B: int, is_int16: bool):
         key = (B, is_int16)
@@ -268,8 +260,10 @@ class AudioFeaturizer:
     @torch.no_grad()
     def __call__(self, pcm: PcmLike, lens=None) -> Tuple[torch.Tensor, torch.Tensor]:
         pcm, lens = self._pack(pcm, lens)
+        is_i16 = pcm.dtype == torch.int16                # of the PCM handed in: the default gain's
+        if self._rs is not None:
+            pcm, lens = self._pack(*self._rs(pcm, lens))
         B, S = pcm.shape
-        is_i16 = pcm.dtype == torch.int16
         if self.use_kernels:
             pcm = pcm.to(self.device, non_blocking=True).contiguous()
             if lens is not None:
@@ -325,6 +319,8 @@ class FeatureStream:
         self.emitted = 0                             # frames emitted so far
         self.finished = False
         self.last_frames: Optional[torch.Tensor] = None
+        self.rs = fz._rs.stream(batch) if fz._rs is not None else None   # input_rate: resample first
+        self.src_i16: Optional[bool] = None          # dtype of the PCM handed in (default gain)
 
     @torch.no_grad()
     def push(self, chunk, final: bool = False, lens=None) -> torch.Tensor:
@@ -338,6 +334,11 @@ class FeatureStream:
         chunk, lens = fz._pack(chunk, lens)
         if chunk.shape[0] != self.B:
             raise ValueError("chunk must be [%d, S_c]" % self.B)
+        if self.src_i16 is None:
+            self.src_i16 = chunk.dtype == torch.int16
+        if self.rs is not None:                      # the resampler's new outputs are this push's chunk
+            chunk = self.rs.push(chunk, final, lens)
+            chunk, lens = fz._pack(chunk, self.rs.last_lens if final else None)
         dev = fz.device if fz.use_kernels else torch.device("cpu")
         chunk = chunk.to(dev)
         if self.buf is None:
@@ -356,7 +357,7 @@ class FeatureStream:
         if t_new == 0:
             self.last_frames = torch.zeros(self.B, dtype=torch.int32, device=fz.device)
             return torch.zeros(self.B, 0, NUM_FEATURES, dtype=fz.out_dtype, device=fz.device)
-        is_i16 = self.buf.dtype == torch.int16
+        is_i16 = self.src_i16
         if fz.use_kernels:
             offset, gain = fz._fixed_stats(self.B, is_i16)
             out, self.last_frames = fz._launch(self.buf.contiguous(), lens, offset, gain, self.lead, mode, t_new)

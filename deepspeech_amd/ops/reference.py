@@ -540,3 +540,70 @@ def seq_dropout_ref(x: torch.Tensor, seed: int, step: int, first_utt: int, site:
     scale = seq_dropout_scale(thr)
     y = (x.float() * scale).to(x.dtype) if x.dtype in (torch.bfloat16, torch.float16) else x * scale
     return torch.where(keep, y, torch.zeros((), dtype=x.dtype, device=x.device))
+
+
+# ---- audio resampling (ops/resample.py, csrc/resample.hip) --------------------------------
+RESAMPLE_ZEROS = 24          # Z: sinc zero crossings on each side at the lower of the two rates
+RESAMPLE_ROLLOFF = 0.90
+RESAMPLE_BETA = 8.0          # Kaiser window
+
+
+def resample_table(in_rate: int, out_rate: int) -> Tuple[int, int, int, np.ndarray]:
+    """(L, M, K, h) of the polyphase windowed-sinc resampler in_rate -> out_rate: L = out / gcd,
+    M = in / gcd, K = 2 ceil(Z max(1, M / L)) taps per output and h [L, K] fp64 with
+    d = k - (K/2 - 1) - ph / L, h = scale sinc(scale d) I0(beta sqrt(1 - (d / (K/2))^2)) / I0(beta),
+    scale = min(1, L / M) rolloff, 0 where |d| > K/2. Not renormalised."""
+    in_rate, out_rate = int(in_rate), int(out_rate)
+    if in_rate <= 0 or out_rate <= 0:
+        raise ValueError("sample rates must be positive")
+    g = int(np.gcd(in_rate, out_rate))
+    L, M = out_rate // g, in_rate // g
+    K = 2 * (-((-RESAMPLE_ZEROS * max(L, M)) // L))
+    scale = min(1.0, L / M) * RESAMPLE_ROLLOFF
+    half = K // 2
+    d = (np.arange(K, dtype=np.float64)[None, :] - (half - 1)) - np.arange(L, dtype=np.float64)[:, None] / L
+    r = 1.0 - (d / half) ** 2
+    win = np.where(r >= 0, np.i0(RESAMPLE_BETA * np.sqrt(np.maximum(r, 0.0))) / np.i0(RESAMPLE_BETA), 0.0)
+    return L, M, K, scale * np.sinc(scale * d) * win
+
+
+def resample_out_len(S: int, L: int, M: int) -> int:
+    """N(S) = ceil(S L / M): outputs of a row of S samples."""
+    return -((-int(S) * int(L)) // int(M))
+
+
+def resample_emitted(P: int, L: int, M: int, K: int) -> int:
+    """E(P) = max(0, ceil((P - K/2) L / M)): outputs whose last tap lies inside the first P input
+    samples, i.e. what a stream has emitted once P samples have arrived."""
+    return max(0, -((-(int(P) - int(K) // 2) * int(L)) // int(M)))
+
+
+def resample_ref(x, in_rate: int, out_rate: int, lens=None, return_abs: bool = False):
+    """fp64 oracle: x [B, S] (or [S]) -> y [B, N(S)] with y[n] = sum_k h[ph, k] x[i - (K/2 - 1) + k],
+    i = n M // L, ph = n M % L, x outside [0, lens[b]) read as +0 by selection; columns at or past
+    N(lens[b]) are zeros. ``return_abs`` adds sum_k |h x| per output (the scale of the rounding
+    bound of a fp32 evaluation)."""
+    x = np.asarray(x)
+    one = x.ndim == 1
+    x = np.atleast_2d(x).astype(np.float64)
+    B, S = x.shape
+    L, M, K, h = resample_table(in_rate, out_rate)
+    ns = [S] * B if lens is None else [int(v) for v in np.asarray(lens).reshape(-1)]
+    N = resample_out_len(S, L, M)
+    y = np.zeros((B, N), np.float64)
+    a = np.zeros((B, N), np.float64)
+    half = K // 2
+    for b in range(B):
+        sb = min(max(ns[b], 0), S)
+        xp = np.zeros(S + K, np.float64)
+        xp[half - 1:half - 1 + sb] = x[b, :sb]            # selection: nothing past sb is read
+        nb = resample_out_len(sb, L, M)
+        for n0 in range(0, nb, 8192):
+            n = np.arange(n0, min(nb, n0 + 8192), dtype=np.int64)
+            t = n * M
+            taps = xp[(t // L)[:, None] + np.arange(K)[None, :]] * h[t % L]
+            y[b, n] = taps.sum(1)
+            a[b, n] = np.abs(taps).sum(1)
+    if one:
+        y, a = y[0], a[0]
+    return (y, a) if return_abs else y

@@ -4,7 +4,7 @@ beam-search decoder on one MI355X).
 
   python tools/bench_infer.py [--layers 5] [--hidden 800] [--seconds 20] [--chunks 0.25,0.5,1.0]
                               [--batches 1,32] [--decoders greedy,beam] [--audio] [--lm ORDER]
-                              [--lookahead TAU]
+                              [--lookahead TAU] [--audio_rate R[,R...]]
 
 RTF = compute seconds / audio seconds per stream (B concurrent streams share each chunk
 launch, so B streams at RTF r serve B * (1 / r) x real time). Random-init weights and
@@ -14,6 +14,9 @@ RTF includes the featurization (csrc/featurize.hip). ``--lm ORDER`` fuses a char
 of that order, trained on seeded synthetic text, into the beam decoder (deepspeech_amd/lm.py).
 ``--lookahead TAU`` puts a lookahead convolution over TAU future frames above the recurrent stack
 (random weights); the RTF then includes its streaming step and the flush in finish().
+``--audio_rate R`` (with ``--audio``) makes the synthetic PCM R Hz, resampled to 16 kHz on the
+device inside the RTF (csrc/resample.hip); several rates, e.g. ``16000,48000``, run one after the
+other in the same process so their RTFs can be read side by side.
 """
 import argparse
 import json
@@ -26,6 +29,24 @@ import torch  # noqa: E402
 
 from deepspeech_amd.infer import rtf  # noqa: E402
 from deepspeech_amd.models import DeepSpeech2  # noqa: E402
+
+
+def bench_one(a, m, eng, data, lm, extra, B, c, d, R):
+    kw = dict(extra)
+    if a.audio:
+        kw.update(audio_rate=R)
+    if lm is not None and d == "beam":
+        kw.update(lm=lm, lm_weight=a.lm_weight, label_bonus=a.label_bonus)
+    r, _ = rtf(m, seconds=a.seconds, chunk_s=c, batch=B, decoder=d, beam_width=a.beam_width, **kw)
+    print(json.dumps({"metric": "streaming RTF (lower is better)", "model": "DS2 2xconv(32) + %dx uni-%s-%d"
+                      % (a.layers, a.cell.upper(), a.hidden), "engine": eng, "streams": B,
+                      "chunk_s": c, "decoder": d, "lookahead": a.lookahead, "beam_width": a.beam_width if d == "beam" else None,
+                      "rtf": round(r, 5), "x_realtime_per_stream": round(1.0 / r, 1) if r > 0 else None,
+                      "x_realtime_total": round(B / r, 1) if r > 0 else None,
+                      "audio_s": a.seconds, "data": data, **({"audio_rate": R} if a.audio else {}),
+                      **({"lm_order": a.lm, "lm_states": int(lm.compile()[0].shape[0])}
+                         if "lm" in kw else {})}),
+          flush=True)
 
 
 def main():
@@ -46,7 +67,10 @@ def main():
     ap.add_argument("--label_bonus", type=float, default=0.5)
     ap.add_argument("--lookahead", type=int, default=0, metavar="TAU",
                     help="lookahead convolution over TAU future frames (0: none)")
+    ap.add_argument("--audio_rate", default="16000", metavar="R[,R...]",
+                    help="sample rate(s) of the synthetic PCM of --audio (other than 16000: resampled on the device)")
     a = ap.parse_args()
+    rates = [int(x) for x in a.audio_rate.split(",")] if a.audio else [16000]
     lm = None
     if a.lm > 0:
         from deepspeech_amd.lm import CharNgramLM, synthetic_corpus
@@ -63,22 +87,14 @@ def main():
             m.lookahead_weight.normal_(0.0, (a.lookahead + 1) ** -0.5)
     m.set_engine(eng, torch.bfloat16 if eng == "hip" else torch.float32)
     rtf(m, seconds=2.0, chunk_s=0.5, batch=1, **extra)  # warm-up (plans, kernels, allocator)
+    for R in rates:
+        if R != 16000:
+            rtf(m, seconds=2.0, chunk_s=0.5, batch=1, audio_rate=R, **extra)  # warm-up of the resampler
     for B in [int(x) for x in a.batches.split(",")]:
         for c in [float(x) for x in a.chunks.split(",")]:
             for d in a.decoders.split(","):
-                kw = dict(extra)
-                if lm is not None and d == "beam":
-                    kw.update(lm=lm, lm_weight=a.lm_weight, label_bonus=a.label_bonus)
-                r, _ = rtf(m, seconds=a.seconds, chunk_s=c, batch=B, decoder=d, beam_width=a.beam_width, **kw)
-                print(json.dumps({"metric": "streaming RTF (lower is better)", "model": "DS2 2xconv(32) + %dx uni-%s-%d"
-                                  % (a.layers, a.cell.upper(), a.hidden), "engine": eng, "streams": B,
-                                  "chunk_s": c, "decoder": d, "lookahead": a.lookahead, "beam_width": a.beam_width if d == "beam" else None,
-                                  "rtf": round(r, 5), "x_realtime_per_stream": round(1.0 / r, 1) if r > 0 else None,
-                                  "x_realtime_total": round(B / r, 1) if r > 0 else None,
-                                  "audio_s": a.seconds, "data": data,
-                                  **({"lm_order": a.lm, "lm_states": int(lm.compile()[0].shape[0])}
-                                     if "lm" in kw else {})}),
-                      flush=True)
+                for R in rates:
+                    bench_one(a, m, eng, data, lm, extra, B, c, d, R)
 
 
 if __name__ == "__main__":
