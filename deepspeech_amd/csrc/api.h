@@ -290,7 +290,7 @@ int ds2_specaug_apply(const float* x, const int* lens, const int* plan, const fl
 int ds2_seq_dropout(const void* x, void* out, const int* ctr, int T, int N, int H, unsigned seed_lo,
                     unsigned seed_hi, int site, int thr, float scale, int locked, hipStream_t st);
 
-// ---- conv_frontend.hip ------------------------------------------------------------------
+// ---- conv1.hip, conv2.hip, bn_cl.hip (shared layer: conv_common.h, bn_math.h) -----------
 // optional BatchNorm-backward apply fused into conv1's weight-gradient staging
 struct DS2Conv1WgradBn {
   const void *dz, *y1;                             // bf16 [N][T1][F1][32]
@@ -304,6 +304,9 @@ struct DS2Conv2DgradBn {
   float* part;                                     // [grid][32][2]
 };
 
+// what a negative return code of the launchers below refused (ConvStatus in conv_common.h); null
+// for any other code
+const char* ds2_conv_status_str(int rc);
 size_t ds2_conv2_fwd_smem(int F1);
 size_t ds2_conv2_dgrad_smem(int F2);
 size_t ds2_conv2_wgrad_smem(int F1);

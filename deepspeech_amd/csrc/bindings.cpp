@@ -25,6 +25,12 @@ hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 void check(int rc, const char* what) {
   TORCH_CHECK(rc == 0, "deepspeech_amd kernel launch failed in ", what, " (code ", rc, ")");
 }
+// the conv front-end's launchers: the message also says what was refused
+void check_conv(int rc, const char* what) {
+  const char* why = ds2_conv_status_str(rc);
+  TORCH_CHECK(rc == 0, "deepspeech_amd kernel launch failed in ", what, " (code ", rc, ")", why ? ": " : "",
+              why ? why : "");
+}
 
 // ---- cross-stream ordering on one device ------------------------------------------------
 // Events keep the default (system-scope) fences: with hipEventReleaseToDevice the next kernel
@@ -580,8 +586,8 @@ void conv1_fwd(at::Tensor x, at::Tensor w, OptT bias, at::Tensor y, at::Tensor p
   const int N = (int)x.size(0), T = (int)x.size(1), F0 = (int)x.size(2), T1 = (int)y.size(1), F1 = (int)y.size(2);
   TORCH_CHECK(y.size(0) == N, "conv1_fwd batch");
   need_f32(part, "part", (int64_t)ds2_conv1_fwd_grid(N, T1) * 64);
-  check(ds2_conv1_fwd(x.data_ptr(), w.data_ptr(), ptr_or_null<float>(bias, "bias"), y.data_ptr(),
-                      part.data_ptr<float>(), N, T, F0, T1, F1, cur_stream()), "conv1_fwd");
+  check_conv(ds2_conv1_fwd(x.data_ptr(), w.data_ptr(), ptr_or_null<float>(bias, "bias"), y.data_ptr(),
+                           part.data_ptr<float>(), N, T, F0, T1, F1, cur_stream()), "conv1_fwd");
 }
 int64_t conv1_fwd_grid(int64_t N, int64_t T1) { return ds2_conv1_fwd_grid((int)N, (int)T1); }
 
@@ -600,9 +606,9 @@ void conv2_fwd(at::Tensor x, at::Tensor w, OptT bias, at::Tensor y, at::Tensor p
               "conv2_fwd shapes");
   TORCH_CHECK(grid > 0, "grid");
   need_f32(part, "part", grid * 64);
-  check(ds2_conv2_fwd(x.data_ptr(), w.data_ptr(), ptr_or_null<float>(bias, "bias"), y.data_ptr(),
-                      part.data_ptr<float>(), (int)grid, (int)x.size(0), (int)x.size(1), (int)x.size(2),
-                      (int)y.size(1), (int)y.size(2), trace_ptr(trace), cur_stream()), "conv2_fwd");
+  check_conv(ds2_conv2_fwd(x.data_ptr(), w.data_ptr(), ptr_or_null<float>(bias, "bias"), y.data_ptr(),
+                           part.data_ptr<float>(), (int)grid, (int)x.size(0), (int)x.size(1), (int)x.size(2),
+                           (int)y.size(1), (int)y.size(2), trace_ptr(trace), cur_stream()), "conv2_fwd");
 }
 
 // dy [N,T2,F2,32], w [32,32,10,5] -> dx [N,T1,F1,32]
@@ -625,10 +631,10 @@ void conv2_dgrad(at::Tensor dy, at::Tensor w, at::Tensor dx, int64_t grid, OptT 
     bn = DS2Conv2DgradBn{y1->data_ptr(), mean->data_ptr<float>(), invstd->data_ptr<float>(),
                          gamma->data_ptr<float>(), beta->data_ptr<float>(), part->data_ptr<float>()};
   }
-  check(ds2_conv2_dgrad(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), (int)grid, (int)dx.size(0), (int)dx.size(1),
-                        (int)dx.size(2), (int)dy.size(1), (int)dy.size(2), with_bn ? &bn : nullptr,
-                        trace_ptr(trace), cur_stream()),
-        "conv2_dgrad");
+  check_conv(ds2_conv2_dgrad(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), (int)grid, (int)dx.size(0), (int)dx.size(1),
+                             (int)dx.size(2), (int)dy.size(1), (int)dy.size(2), with_bn ? &bn : nullptr,
+                             trace_ptr(trace), cur_stream()),
+             "conv2_dgrad");
 }
 
 // dy [N,T2,F2,32], x [N,T1,F1,32] -> dw (fp32, 32*32*10*5), part scratch
@@ -637,9 +643,9 @@ void conv2_wgrad(at::Tensor dy, at::Tensor x, at::Tensor part, at::Tensor dw, in
   TORCH_CHECK(grid > 0, "grid");
   need_f32(part, "part", ds2_conv2_wgrad_part_floats((int)grid));
   need_f32(dw, "dw", 32 * 32 * 50);
-  check(ds2_conv2_wgrad(dy.data_ptr(), x.data_ptr(), part.data_ptr<float>(), (int)grid, dw.data_ptr<float>(),
-                        (int)x.size(0), (int)x.size(1), (int)x.size(2), (int)dy.size(1), (int)dy.size(2),
-                        cur_stream()), "conv2_wgrad");
+  check_conv(ds2_conv2_wgrad(dy.data_ptr(), x.data_ptr(), part.data_ptr<float>(), (int)grid, dw.data_ptr<float>(),
+                             (int)x.size(0), (int)x.size(1), (int)x.size(2), (int)dy.size(1), (int)dy.size(2),
+                             cur_stream()), "conv2_wgrad");
 }
 
 // dy [N,T1,F1,32], x [N,T,F0] -> dw (fp32, 32*20*5)
@@ -663,9 +669,9 @@ void conv1_wgrad(at::Tensor dy, at::Tensor x, at::Tensor part, at::Tensor dw, in
                          gamma->data_ptr<float>(), beta->data_ptr<float>(), dbeta->data_ptr<float>(),
                          dgamma->data_ptr<float>()};
   }
-  check(ds2_conv1_wgrad(with_bn ? nullptr : dy.data_ptr(), x.data_ptr(), part.data_ptr<float>(), (int)grid,
-                        dw.data_ptr<float>(), (int)x.size(0), (int)x.size(1), (int)x.size(2), (int)dy.size(1),
-                        (int)dy.size(2), with_bn ? &bn : nullptr, cur_stream()), "conv1_wgrad");
+  check_conv(ds2_conv1_wgrad(with_bn ? nullptr : dy.data_ptr(), x.data_ptr(), part.data_ptr<float>(), (int)grid,
+                             dw.data_ptr<float>(), (int)x.size(0), (int)x.size(1), (int)x.size(2), (int)dy.size(1),
+                             (int)dy.size(2), with_bn ? &bn : nullptr, cur_stream()), "conv1_wgrad");
 }
 int64_t conv2_wgrad_part_floats(int64_t grid) { return ds2_conv2_wgrad_part_floats((int)grid); }
 int64_t conv1_wgrad_part_floats(int64_t grid) { return ds2_conv1_wgrad_part_floats((int)grid); }
@@ -674,9 +680,10 @@ void bn_cl_finalize(at::Tensor part, int64_t nb, double M, double eps, at::Tenso
                     OptT run_mean, OptT run_var, double momentum) {
   need_f32(part, "part", nb * 64);
   need_f32(mean, "mean", 32); need_f32(invstd, "invstd", 32);
-  check(ds2_bn_cl_finalize(part.data_ptr<float>(), (int)nb, M, (float)eps, mean.data_ptr<float>(),
-                           invstd.data_ptr<float>(), ptr_or_null<float>(run_mean, "run_mean"),
-                           ptr_or_null<float>(run_var, "run_var"), (float)momentum, cur_stream()), "bn_cl_finalize");
+  check_conv(ds2_bn_cl_finalize(part.data_ptr<float>(), (int)nb, M, (float)eps, mean.data_ptr<float>(),
+                                invstd.data_ptr<float>(), ptr_or_null<float>(run_mean, "run_mean"),
+                                ptr_or_null<float>(run_var, "run_var"), (float)momentum, cur_stream()),
+             "bn_cl_finalize");
 }
 
 // y [N,T,F,32] -> out [N,T,F,32] (tmaj=0) or [T,N,32*F] (tmaj=1)
@@ -685,9 +692,9 @@ void bn_cl_apply(at::Tensor y, at::Tensor mean, at::Tensor invstd, at::Tensor ga
   need_bf16(y, "y"); need_bf16(out, "out");
   TORCH_CHECK(y.dim() == 4 && y.size(3) == 32 && out.numel() == y.numel(), "bn_cl_apply shapes");
   need_f32(mean, "mean", 32); need_f32(invstd, "invstd", 32); need_f32(gamma, "gamma", 32); need_f32(beta, "beta", 32);
-  check(ds2_bn_cl_apply(y.data_ptr(), mean.data_ptr<float>(), invstd.data_ptr<float>(), gamma.data_ptr<float>(),
-                        beta.data_ptr<float>(), out.data_ptr(), (int)y.size(0), (int)y.size(1), (int)y.size(2),
-                        tmaj ? 1 : 0, cur_stream()), "bn_cl_apply");
+  check_conv(ds2_bn_cl_apply(y.data_ptr(), mean.data_ptr<float>(), invstd.data_ptr<float>(), gamma.data_ptr<float>(),
+                             beta.data_ptr<float>(), out.data_ptr(), (int)y.size(0), (int)y.size(1), (int)y.size(2),
+                             tmaj ? 1 : 0, cur_stream()), "bn_cl_apply");
 }
 
 // part_ready: part already holds nb partial sums (conv2_dgrad's bn epilogue), skip the reduce pass;
@@ -701,10 +708,10 @@ void bn_cl_bwd(at::Tensor dz, at::Tensor y, at::Tensor mean, at::Tensor invstd, 
   need_f32(part, "part", nb * 64);
   need_f32(mean, "mean", 32); need_f32(invstd, "invstd", 32); need_f32(gamma, "gamma", 32); need_f32(beta, "beta", 32);
   need_f32(dgamma, "dgamma", 32); need_f32(dbeta, "dbeta", 32);
-  check(ds2_bn_cl_bwd(dz.data_ptr(), y.data_ptr(), mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                      gamma.data_ptr<float>(), beta.data_ptr<float>(), part.data_ptr<float>(), (int)nb,
-                      dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), dy.data_ptr(), (int)y.size(0),
-                      (int)y.size(1), (int)y.size(2), tmaj ? 1 : 0, (int)part_ready, cur_stream()), "bn_cl_bwd");
+  check_conv(ds2_bn_cl_bwd(dz.data_ptr(), y.data_ptr(), mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                           gamma.data_ptr<float>(), beta.data_ptr<float>(), part.data_ptr<float>(), (int)nb,
+                           dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), dy.data_ptr(), (int)y.size(0),
+                           (int)y.size(1), (int)y.size(2), tmaj ? 1 : 0, (int)part_ready, cur_stream()), "bn_cl_bwd");
 }
 
 // --------------------------------------------------------------------------- greedy CTC decode

@@ -9,14 +9,13 @@
 // Statistics: per-(channel, chunk) partial sums in fp32 (sum, sum of squares about a
 // per-channel shift = first element, which keeps the one-pass variance well conditioned),
 // combined in fp64 by a finalize kernel that also updates the running statistics.
-#include "common.h"
+#include "bn_math.h"
 
 using namespace ds2;
 
 namespace {
 
 constexpr int BN_THREADS = 256;
-constexpr float CLIP = 20.0f;
 
 template <typename T> __device__ __forceinline__ float ldf(const T* p);
 template <> __device__ __forceinline__ float ldf<float>(const float* p) { return *p; }
@@ -107,11 +106,10 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(const TI* __restri
   const int c = blockIdx.y;
   const int TF = T * F;
   const size_t M = (size_t)N * TF;
-  const float sc = invstd[c] * gamma[c];
-  const float sh = beta[c] - mean[c] * sc;
+  float sc, sh;
+  bn_scale_shift(mean[c], invstd[c], gamma[c], beta[c], sc, sh);
   for (size_t i = (size_t)blockIdx.x * BN_THREADS + threadIdx.x; i < M; i += (size_t)gridDim.x * BN_THREADS) {
-    const float v = ldf<TI>(y + nchw_idx(i, c, C, TF));
-    const float z = fminf(fmaxf(v * sc + sh, 0.f), CLIP);
+    const float z = bn_clip(ldf<TI>(y + nchw_idx(i, c, C, TF)), sc, sh);
     const size_t o = layout == 0 ? nchw_idx(i, c, C, TF) : tmaj_idx(i, c, N, C, T, F);
     stf<TO>(out + o, z);
   }
@@ -130,10 +128,9 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_reduce_kernel(
   const float mu = mean[c], is = invstd[c], g = gamma[c], bt = beta[c];
   float s = 0.f, q = 0.f;
   for (size_t i = (size_t)j * BN_THREADS + threadIdx.x; i < M; i += (size_t)nb * BN_THREADS) {
-    const float xh = (ldf<TI>(y + nchw_idx(i, c, C, TF)) - mu) * is;
-    const float z = xh * g + bt;
+    const float xh = bn_xhat(ldf<TI>(y + nchw_idx(i, c, C, TF)), mu, is);
     const size_t o = layout == 0 ? nchw_idx(i, c, C, TF) : tmaj_idx(i, c, N, C, T, F);
-    const float dz = (z > 0.f && z < CLIP) ? ldf<TG>(dout + o) : 0.f;
+    const float dz = bn_unclipped(xh, g, bt) ? ldf<TG>(dout + o) : 0.f;
     s += dz;
     q += dz * xh;
   }
@@ -171,11 +168,10 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply_kernel(
   const float k = g * is;
   for (size_t i = (size_t)blockIdx.x * BN_THREADS + threadIdx.x; i < M; i += (size_t)gridDim.x * BN_THREADS) {
     const size_t src = nchw_idx(i, c, C, TF);
-    const float xh = (ldf<TI>(y + src) - mu) * is;
-    const float z = xh * g + bt;
+    const float xh = bn_xhat(ldf<TI>(y + src), mu, is);
     const size_t o = layout == 0 ? src : tmaj_idx(i, c, N, C, T, F);
-    const float dz = (z > 0.f && z < CLIP) ? ldf<TG>(dout + o) : 0.f;
-    stf<TD>(dy + src, k * (dz - mdb - xh * mdg));
+    const float dz = bn_unclipped(xh, g, bt) ? ldf<TG>(dout + o) : 0.f;
+    stf<TD>(dy + src, bn_bwd_value(k, dz, xh, mdb, mdg));
   }
 }
 

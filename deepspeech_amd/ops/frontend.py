@@ -1,7 +1,7 @@
 """Conv front-end on the HIP engine.
 
 Default (32 filters, the reference geometry): FrontendCL — the channels-last implicit-GEMM
-MFMA kernels of csrc/conv_frontend.hip for conv fwd / dgrad / wgrad with BatchNorm
+MFMA kernels of csrc/conv1.hip and csrc/conv2.hip for conv fwd / dgrad / wgrad with BatchNorm
 statistics fused into the conv epilogues and channels-last BN + clipped-ReLU kernels; the
 conv2 BN apply writes the RNN input directly in time-major [T2, N, C*F2] order (reference
 transpose+reshape, src/deepSpeech_NCHW.py:166-168).
@@ -225,7 +225,7 @@ def _zero_grad_of(p: torch.Tensor):
 
 
 class FrontendCL(torch.autograd.Function):
-    """Whole conv front-end on the channels-last MFMA kernels of csrc/conv_frontend.hip.
+    """Whole conv front-end on the channels-last MFMA kernels of csrc/conv1.hip, conv2.hip and bn_cl.hip.
 
     feats [N, T, F0] -> time-major RNN input [T2, N, 32*F2] (bf16). Forward: conv1 (+bias,
     BN statistics in the epilogue) -> BN finalize -> BN+clip apply -> conv2 (+bias, stats)
@@ -356,7 +356,7 @@ class FrontendCL(torch.autograd.Function):
         return None, gw1, gbias1, gg1, gb1, gw2, gbias2, gg2, gb2, None
 
 
-# F1 = (F0-5)//2+1 frequency positions each pass of csrc/conv_frontend.hip takes. The forward
+# F1 = (F0-5)//2+1 frequency positions each pass of csrc/conv1.hip / conv2.hip takes. The forward
 # kernels cover 9..80. A training step also runs ds2_conv2_dgrad, whose gate refuses F1 <= 64
 # (code -42: it stores positions 0..63 of a row unchecked), so training needs 65..80 (133..163
 # bins); every other kernel of the backward pass takes the forward range.

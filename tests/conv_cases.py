@@ -1,5 +1,5 @@
 """Step-local fp64 oracle, per-element checker, guard-banded buffers and case tables of the conv
-front-end kernels (csrc/conv_frontend.hip) and the NCHW BatchNorm kernels (csrc/bn_act.hip).
+front-end kernels (csrc/conv1.hip, conv2.hip, bn_cl.hip) and the NCHW BatchNorm kernels (csrc/bn_act.hip).
 Pure torch, device-agnostic, does not import the extension.
 
 Geometry: F1 = (F0-5)//2+1, F2 = F1-4, T1 = (T-20)//2+1, T2 = (T1-10)//2+1. Layouts are the

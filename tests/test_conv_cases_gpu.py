@@ -1,4 +1,4 @@
-"""Conv front-end kernels (csrc/conv_frontend.hip) and the NCHW BatchNorm kernels (csrc/bn_act.hip)
+"""Conv front-end kernels (csrc/conv1.hip, conv2.hip, bn_cl.hip) and the NCHW BatchNorm kernels (csrc/bn_act.hip)
 per element against the step-local fp64 oracle of tests/conv_cases.py, whose docstring holds the
 method, the two input families and every tolerance. Each kernel is called through its binding on
 the case tables there; every output and partials buffer sits between guard bands.
@@ -136,6 +136,35 @@ def test_conv2_dgrad_refuses_narrow_rows(cuda):
         C_.conv2_dgrad(dy, w, dx.t, 4)
     torch.cuda.synchronize()
     dx.verify("refused conv2_dgrad", written=False)
+
+
+def test_refusals_name_their_condition(cuda):
+    """Three host gates at their smallest shapes: conv1_fwd with an F1 = 97 output against F0 = 161
+    (F1 must be (161 - 5) // 2 + 1 = 79), bn_cl_apply on F = 97 > 96, conv2_dgrad at F1 = 64. Each
+    raises a RuntimeError that names its own condition, and no buffer, input or output, changes."""
+    C_ = _ext()
+    vec = [G((32,), F32, cuda) for _ in range(4)]
+    x, w1, y1 = G((1, 20, 161), BFT, cuda), G((32, 1, 20, 5), BFT, cuda), G((1, 1, 97, 32), BFT, cuda)
+    part = G((int(C_.conv1_fwd_grid(1, 1)) * 64,), F32, cuda)
+    ya, za = G((1, 1, 97, 32), BFT, cuda), G((1, 1, 97, 32), BFT, cuda)
+    dy, w2, dx = G((1, 1, 60, 32), BFT, cuda), G((32, 32, 10, 5), BFT, cuda), G((1, 10, 64, 32), BFT, cuda)
+    calls = {
+        "conv1_fwd": (lambda: C_.conv1_fwd(x.t, w1.t, None, y1.t, part.t), r"F1 = \(F0 - 5\) / 2 \+ 1"),
+        "bn_cl_apply": (lambda: C_.bn_cl_apply(ya.t, *(v.t for v in vec), za.t, False), r"F <= 96"),
+        "conv2_dgrad": (lambda: C_.conv2_dgrad(dy.t, w2.t, dx.t, 4), r"F1 > 64"),
+    }
+    said = {}
+    for name, (call, condition) in calls.items():
+        pattern = r"kernel launch failed in %s \(code -\d+\): .*%s" % (name, condition)
+        with pytest.raises(RuntimeError, match=pattern) as e:
+            call()
+        said[name] = str(e.value).split("\n")[0].split("kernel launch failed in ")[1]
+    torch.cuda.synchronize()
+    texts = [s.split(": ", 1)[1] for s in said.values()]
+    codes = [s.split("(code ")[1].split(")")[0] for s in said.values()]
+    assert len(set(texts)) == 3 and len(set(codes)) == 3, said
+    for b in vec + [x, w1, y1, part, ya, za, dy, w2, dx]:
+        b.verify("refused call", written=False)
 
 
 @pytest.mark.parametrize("c", CO.CONV2_WGRAD, ids=CO.ident)

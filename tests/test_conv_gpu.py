@@ -1,4 +1,4 @@
-"""Conv front-end MFMA kernels (csrc/conv_frontend.hip) against plain-PyTorch fp32 references.
+"""Conv front-end MFMA kernels (csrc/conv1.hip, conv2.hip, bn_cl.hip) against plain-PyTorch fp32 references.
 
 Each kernel is checked on its own (conv1/conv2 forward, conv2 data gradient, conv1/conv2
 weight gradients, channels-last BatchNorm statistics/apply/backward), then the whole
