@@ -134,6 +134,11 @@ def build_train_parser() -> argparse.ArgumentParser:
     p.add_argument("--rnn_dropout_mode", type=str, default="element", choices=["element", "locked"],
                    help="element: one draw per frame, utterance and unit; locked: one per utterance and "
                         "unit, shared by all frames")
+    p.add_argument("--max_grad_norm", type=float, default=0.0,
+                   help="clip the global gradient norm (of the data-parallel mean) at this value "
+                        "(ops/reference.py clip_coef_ref; Deep Speech 2 used 400), inf = measure only, 0 = off. "
+                        "A step whose norm is not finite updates nothing. A training hyper-parameter: a "
+                        "resume may change it, evaluation never reads it")
     p.add_argument("--device", type=str, default="auto", help="auto | cpu | cuda")
     p.add_argument("--gpus", type=int, default=None,
                    help="ranks (one per GPU) on this node; without an outer launcher (torchrun) the driver "

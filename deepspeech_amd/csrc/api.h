@@ -232,12 +232,20 @@ int ds2_bn_bwd(const void* dout, int dout_bf16, const void* y, int y_bf16, const
 // ---- optim.hip, reduce.hip, stats.hip ---------------------------------------------------
 int ds2_adam_ema(float* p, const float* g, float* m, float* v, float* ema, void* p16, long long n, float lr_t,
                  float b1, float b2, float eps, float gscale, float ema_keep, const int* skip, int max_grid,
-                 const float* hyper, int lds_reserve, hipStream_t st);
+                 const float* hyper, int lds_reserve, const float* clip, hipStream_t st);
 int ds2_adam_ema_ranges(float* p, const float* g, float* m, float* v, float* ema, void* p16, const long long* lohi,
                         int nr, float lr_t, float b1, float b2, float eps, float gscale, float ema_keep,
-                        const float* hyper, hipStream_t st);
+                        const float* hyper, const float* clip, hipStream_t st);
 int ds2_grad_norm_blocks(long long n);
 int ds2_grad_norm(const float* g, long long n, float gscale, float* part, int nblocks, int* bad, hipStream_t st);
+// gradient-norm clipping: per-segment partial sums of squares, then {S, norm, coef, bad, steps,
+// clipped_steps, skipped_steps, spare} (ds2_clip_state_words() 4-byte words) read by the updates
+// that are given the state as `clip`
+int ds2_grad_sumsq_segment(void);
+int ds2_clip_state_words(void);
+int ds2_grad_sumsq(const float* g, long long n, float gscale, float* part, int max_grid, int nontemporal,
+                   hipStream_t st);
+int ds2_clip_finalize(const float* part, long long nseg, float max_norm, float* state, hipStream_t st);
 int ds2_cast_bf16(const float* x, void* y, long long n, hipStream_t st);
 int ds2_col_sum(int n, const float* const* in, float* const* out, const int* R, const int* B, const int* C,
                 const int* acc, hipStream_t st);

@@ -517,11 +517,22 @@ static void adam_arrays_check(const at::Tensor& p, const at::Tensor& g, const at
   }
 }
 
+// The clipping state the CLIP kernels read (csrc/optim.hip): ds2_clip_state_words() fp32 words on the GPU
+static void clip_state_check(const OptT& clip, const char* what) {
+  if (clip.has_value() && clip->defined()) {
+    need_gpu(*clip, "clip");
+    TORCH_CHECK(clip->scalar_type() == at::kFloat && clip->numel() >= ds2_clip_state_words() && clip->is_contiguous(),
+                what, ": clip must be the contiguous fp32 clipping state");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(clip->data_ptr()) % 4 == 0, what, ": clip must be 4-byte aligned");
+  }
+}
+
 void adam_ema(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, OptT ema, OptT p16, double lr_t, double b1,
               double b2, double eps, double gscale, double ema_keep, OptT skip, int64_t max_grid, OptT hyper,
-              int64_t lds_reserve) {
+              int64_t lds_reserve, OptT clip) {
   TORCH_CHECK(lds_reserve >= 0 && lds_reserve <= 65536, "adam_ema: lds_reserve in [0, 64 KB]");
   adam_arrays_check(p, g, m, v, ema, p16, hyper, "adam_ema");
+  clip_state_check(clip, "adam_ema");
   if (skip.has_value() && skip->defined()) {
     need_gpu(*skip, "skip");
     TORCH_CHECK(skip->scalar_type() == at::kInt && skip->numel() >= 1, "adam_ema: skip must be an int32 flag");
@@ -530,15 +541,17 @@ void adam_ema(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, OptT ema, 
   check(ds2_adam_ema(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
                      ptr_or_null<float>(ema, "ema"), ptr_or_null<void>(p16, "p16"), n, (float)lr_t, (float)b1,
                      (float)b2, (float)eps, (float)gscale, (float)ema_keep, ptr_or_null<const int>(skip, "skip"),
-                     (int)max_grid, ptr_or_null<const float>(hyper, "hyper"), (int)lds_reserve, cur_stream()),
+                     (int)max_grid, ptr_or_null<const float>(hyper, "hyper"), (int)lds_reserve,
+                     ptr_or_null<const float>(clip, "clip"), cur_stream()),
         "adam_ema");
 }
 
 // Adam + EMA over several (lo, hi) element ranges of whole-arena buffers in one launch
 void adam_ema_ranges(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, OptT ema, OptT p16,
                      std::vector<int64_t> lohi, double lr_t, double b1, double b2, double eps, double gscale,
-                     double ema_keep, OptT hyper) {
+                     double ema_keep, OptT hyper, OptT clip) {
   adam_arrays_check(p, g, m, v, ema, p16, hyper, "adam_ema_ranges");
+  clip_state_check(clip, "adam_ema_ranges");
   const long long n = p.numel();
   TORCH_CHECK(lohi.size() % 2 == 0, "adam_ema_ranges: (lo, hi) pairs");
   for (size_t i = 0; i < lohi.size(); ++i) TORCH_CHECK(lohi[i] >= 0 && lohi[i] <= n, "adam_ema_ranges: range");
@@ -553,7 +566,8 @@ void adam_ema_ranges(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, Opt
   check(ds2_adam_ema_ranges(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
                             ptr_or_null<float>(ema, "ema"), ptr_or_null<void>(p16, "p16"), r.data(),
                             (int)(r.size() / 2), (float)lr_t, (float)b1, (float)b2, (float)eps, (float)gscale,
-                            (float)ema_keep, ptr_or_null<const float>(hyper, "hyper"), cur_stream()),
+                            (float)ema_keep, ptr_or_null<const float>(hyper, "hyper"),
+                            ptr_or_null<const float>(clip, "clip"), cur_stream()),
         "adam_ema_ranges");
 }
 
@@ -569,6 +583,35 @@ void grad_norm(at::Tensor g, double gscale, at::Tensor part, at::Tensor bad) {
   check(ds2_grad_norm(g.data_ptr<float>(), g.numel(), (float)gscale, part.data_ptr<float>(), (int)part.numel(),
                       bad.data_ptr<int>(), cur_stream()),
         "grad_norm");
+}
+
+int64_t grad_sumsq_segment() { return ds2_grad_sumsq_segment(); }
+
+// part[ceil(n / segment)] = fixed-order partial sums of (fl32(g gscale))^2, one per segment of g.
+// nontemporal (the default, as measured: profiles/clip.md) only changes the load instruction, never a partial.
+void grad_sumsq(at::Tensor g, double gscale, at::Tensor part, int64_t max_grid, bool nontemporal) {
+  need_gpu(g, "g");
+  need_gpu(part, "part");
+  const int64_t seg = ds2_grad_sumsq_segment();
+  TORCH_CHECK(g.scalar_type() == at::kFloat, "grad_sumsq: fp32 gradients");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(g.data_ptr()) % 16 == 0, "grad_sumsq: g must be 16-byte aligned");
+  TORCH_CHECK(part.scalar_type() == at::kFloat && part.numel() == (g.numel() + seg - 1) / seg,
+              "grad_sumsq: part must hold one fp32 per segment of g");
+  TORCH_CHECK(max_grid >= 0 && max_grid <= 65535, "grad_sumsq: max_grid in [0, 65535]");
+  check(ds2_grad_sumsq(g.data_ptr<float>(), g.numel(), (float)gscale, part.data_ptr<float>(), (int)max_grid,
+                       nontemporal ? 1 : 0, cur_stream()),
+        "grad_sumsq");
+}
+
+// state = {S, norm, coef | bad, steps, clipped_steps, skipped_steps, spare} from the partials and max_norm
+void clip_finalize(at::Tensor part, double max_norm, at::Tensor state) {
+  need_gpu(part, "part");
+  TORCH_CHECK(part.scalar_type() == at::kFloat, "clip_finalize: fp32 partials");
+  TORCH_CHECK(max_norm > 0, "clip_finalize: max_norm must be > 0 (inf: measure only)");
+  OptT st = state;
+  clip_state_check(st, "clip_finalize");
+  check(ds2_clip_finalize(part.data_ptr<float>(), part.numel(), (float)max_norm, state.data_ptr<float>(), cur_stream()),
+        "clip_finalize");
 }
 
 void cast_bf16(at::Tensor x, at::Tensor y) {
@@ -1645,12 +1688,17 @@ PYBIND11_MODULE(_C, m) {
   m.def("adam_ema", &adam_ema, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("ema"),
         py::arg("p16"), py::arg("lr_t"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("gscale"),
         py::arg("ema_keep"), py::arg("skip"), py::arg("max_grid"), py::arg("hyper") = py::none(),
-        py::arg("lds_reserve") = 0);
+        py::arg("lds_reserve") = 0, py::arg("clip") = py::none());
   m.def("adam_ema_ranges", &adam_ema_ranges, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"),
         py::arg("ema"), py::arg("p16"), py::arg("lohi"), py::arg("lr_t"), py::arg("b1"), py::arg("b2"),
-        py::arg("eps"), py::arg("gscale"), py::arg("ema_keep"), py::arg("hyper") = py::none());
+        py::arg("eps"), py::arg("gscale"), py::arg("ema_keep"), py::arg("hyper") = py::none(),
+        py::arg("clip") = py::none());
   m.def("grad_norm_blocks", &grad_norm_blocks);
   m.def("grad_norm", &grad_norm);
+  m.def("grad_sumsq_segment", &grad_sumsq_segment);
+  m.def("grad_sumsq", &grad_sumsq, py::arg("g"), py::arg("gscale"), py::arg("part"), py::arg("max_grid") = 0,
+        py::arg("nontemporal") = true);
+  m.def("clip_finalize", &clip_finalize, py::arg("part"), py::arg("max_norm"), py::arg("state"));
   m.def("cast_bf16", &cast_bf16);
   m.def("device_info", &device_info);
   m.def("fp8_quant_blocks", &fp8_quant_blocks);

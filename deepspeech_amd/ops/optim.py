@@ -408,8 +408,20 @@ def exponential_decay(initial_lr: float, step: int, decay_steps: int, decay_rate
 class FusedAdamEMA:
     """Adam (TF epsilon-hat form) + weight EMA over a ParamArena."""
 
+    # words of the clipping state (csrc/optim.hip CLIP_*): fp32 {S, norm, coef}, int32 {bad, steps,
+    # clipped_steps, skipped_steps}, one spare
+    _CLIP_F = ("sumsq", "grad_norm", "clip_coef")
+    _CLIP_I = ("bad", "steps", "clipped_steps", "skipped_steps")
+
     def __init__(self, arena: ParamArena, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
-                 ema_decay: Optional[float] = 0.9999, bf16_copy: bool = False):
+                 ema_decay: Optional[float] = 0.9999, bf16_copy: bool = False, max_grad_norm: float = 0.0):
+        """``max_grad_norm`` = C > 0 clips the global gradient norm at C (inf: measure the norm,
+        never clip; ops/reference.py has the definition); 0 = off, the update as it always was."""
+        max_grad_norm = float(max_grad_norm)
+        if not max_grad_norm >= 0.0:
+            raise ValueError("max_grad_norm must be >= 0 (0: off, inf: measure only), got %r" % max_grad_norm)
+        self.max_grad_norm = max_grad_norm
+        self.clip = max_grad_norm > 0.0
         self.arena = arena
         self.lr = lr
         self.b1, self.b2 = betas
@@ -431,6 +443,62 @@ class FusedAdamEMA:
         # ``device_hyper`` is set (a captured step: Trainer step graphs); load_hyper() writes it
         self.hyper = torch.zeros(2, device=dev, dtype=torch.float32) if self.use_hip else None
         self.device_hyper = False
+        # gradient-norm clipping: the state measure_norm() writes and the clipped updates read, and
+        # the per-segment partial sums between its two kernels; allocated once (a captured step
+        # bakes their addresses)
+        self.clip_state = self._clip_part = None
+        if self.clip:
+            self.clip_state = torch.zeros(8, device=dev, dtype=torch.float32)
+            if self.use_hip:
+                seg = int(_ext.ext().grad_sumsq_segment())
+                self._clip_part = torch.empty(-(-arena.numel // seg), device=dev, dtype=torch.float32)
+
+    # ---- gradient-norm clipping ---------------------------------------------------------
+    @torch.no_grad()
+    def measure_norm(self, gscale: float = 1.0) -> None:
+        """Measure the norm of the whole (gscale-scaled) gradient arena and derive this step's
+        clipping coefficient into :attr:`clip_state`, on the current stream and without a host
+        synchronisation (GPU: grad_sumsq + clip_finalize). Call once per step, after every
+        gradient is final and before the first :meth:`apply_range` of the step.
+
+        Ordering against a carried update (Trainer defer_update), whose chunks read the previous
+        step's state while they run beside the next forward: the caller enqueues this behind
+        ParamArena.settle_updates() of the current stream (Trainer._body settles right after the
+        forward, the norm is taken after the backward), so every chunk has run before the state
+        is overwritten; one state slot is enough."""
+        if not self.clip:
+            raise RuntimeError("measure_norm: the optimizer was built without max_grad_norm")
+        g = self.arena.grad
+        if self.use_hip:
+            C = _ext.ext()
+            C.grad_sumsq(g, gscale, self._clip_part)
+            C.clip_finalize(self._clip_part, self.max_grad_norm, self.clip_state)
+            return
+        from .reference import clip_coef_ref
+        S, norm, coef, bad = clip_coef_ref(g, gscale, self.max_grad_norm)
+        st, ist = self.clip_state, self.clip_state.view(torch.int32)
+        st[0], st[1], st[2] = S, norm, coef
+        ist[3] = int(bad)
+        ist[4] += 1
+        ist[5] += int(not bad and norm > self.max_grad_norm)
+        ist[6] += int(bad)
+
+    def clip_bad_flag(self) -> torch.Tensor:
+        """int32 [1] view of the state's bad flag (1: this step's norm was not finite and nothing
+        was updated): the skip flag of a clipped step, on the device."""
+        return self.clip_state.view(torch.int32)[3:4]
+
+    def clip_stats(self) -> Dict[str, float]:
+        """The clipping state as Python numbers: sumsq, grad_norm, clip_coef of the last measured
+        step, its bad flag, and the counters steps / clipped_steps / skipped_steps. Copies from
+        the device, i.e. synchronises: call only where the host waits anyway."""
+        if not self.clip:
+            raise RuntimeError("clip_stats: the optimizer was built without max_grad_norm")
+        st = self.clip_state.detach().cpu()
+        out = {k: float(st[i]) for i, k in enumerate(self._CLIP_F)}
+        ist = st.view(torch.int32)
+        out.update({k: int(ist[3 + i]) for i, k in enumerate(self._CLIP_I)})
+        return out
 
     def load_hyper(self, lr_t: float, keep: float) -> None:
         """Stage this update's (lr_t, ema_keep) into :attr:`hyper` on the current stream (an
@@ -475,7 +543,10 @@ class FusedAdamEMA:
         """Adam + EMA of arena elements [lo, hi) with a prepared (lr_t, keep), on the current
         stream. Every element's update is independent and rounds the same way whatever the
         launch split, so ranges compose bitwise into the whole-arena update (the DP bucketer
-        issues one range per gradient bucket)."""
+        issues one range per gradient bucket).
+
+        With ``max_grad_norm`` the clipped update: every range of the step reads the coefficient
+        :meth:`measure_norm` left in :attr:`clip_state`, and none writes anything on a bad step."""
         if hi <= lo:
             return
         a = self.arena
@@ -483,28 +554,40 @@ class FusedAdamEMA:
         if not self.use_hip:
             if skip_flag is not None and int(skip_flag.item()) != 0:
                 return
-            p, m, v = a.flat[sl], self.m[sl], self.v[sl]
-            g = a.grad[sl] * gscale
-            m.mul_(self.b1).add_(g, alpha=1 - self.b1)
-            v.mul_(self.b2).addcmul_(g, g, value=1 - self.b2)
-            p.sub_(lr_t * m / (v.sqrt() + self.eps))
-            if self.ema is not None:
-                e = self.ema[sl]
-                e.copy_(p + keep * (e - p))
-            if self.p16 is not None:
-                self.p16[sl].copy_(p)
+            if not self.clip:
+                p, m, v = a.flat[sl], self.m[sl], self.v[sl]
+                g = a.grad[sl] * gscale
+                m.mul_(self.b1).add_(g, alpha=1 - self.b1)
+                v.mul_(self.b2).addcmul_(g, g, value=1 - self.b2)
+                p.sub_(lr_t * m / (v.sqrt() + self.eps))
+                if self.ema is not None:
+                    e = self.ema[sl]
+                    e.copy_(p + keep * (e - p))
+                if self.p16 is not None:
+                    self.p16[sl].copy_(p)
+                return
+            if int(self.clip_state.view(torch.int32)[3]) != 0:
+                return
+            from .reference import clipped_adam_ref
+            clipped_adam_ref(a.flat[sl], a.grad[sl], self.m[sl], self.v[sl],
+                             self.ema[sl] if self.ema is not None else None,
+                             self.p16[sl] if self.p16 is not None else None,
+                             lr_t, self.b1, self.b2, self.eps, gscale, float(self.clip_state[2]), keep)
             return
         _ext.ext().adam_ema(a.flat[sl], a.grad[sl], self.m[sl], self.v[sl],
                             self.ema[sl] if self.ema is not None else None,
                             self.p16[sl] if self.p16 is not None else None,
                             lr_t, self.b1, self.b2, self.eps, gscale, keep, skip_flag, int(max_grid),
-                            self._hyper_arg(), int(lds_reserve))
+                            self._hyper_arg(), int(lds_reserve), self.clip_state)
 
     @torch.no_grad()
     def step(self, lr: float, global_step: int, gscale: float = 1.0,
              skip_flag: Optional[torch.Tensor] = None) -> None:
-        """One Adam + EMA update of the whole arena."""
+        """One Adam + EMA update of the whole arena (with ``max_grad_norm``: norm, then the
+        clipped update)."""
         lr_t, keep = self.prepare(lr, global_step)
+        if self.clip:
+            self.measure_norm(gscale)
         self.apply_range(0, self.arena.numel, lr_t, keep, gscale, skip_flag)
 
     def state_dict(self) -> Dict[str, object]:

@@ -607,3 +607,69 @@ def resample_ref(x, in_rate: int, out_rate: int, lens=None, return_abs: bool = F
     if one:
         y, a = y[0], a[0]
     return (y, a) if return_abs else y
+
+
+# ---------------------------------------------------------------------------- gradient-norm clipping
+# Definition shared by csrc/optim.hip (grad_sumsq + clip_finalize + the CLIP Adam kernels), the CPU
+# branch of FusedAdamEMA and the tests. With threshold C > 0 (inf: measure only) and
+# x_i = fl32(g_i gscale), the first product of adam1 (csrc/common.h):
+#   S = sum_i x_i^2 over the whole arena      norm = fl32(sqrt(S))
+#   bad  = norm is not finite (a NaN / inf gradient, or S past the fp32 range)
+#   coef = 0 if bad, else 1.0 exactly (selected, never computed) if norm <= C, else fl32(C / norm)
+# A bad step updates nothing. Otherwise every element takes adam1 with g' = fl32(x_i coef) in place
+# of x_i; x * 1.0f is exact, so a step with coef == 1 is bitwise the unclipped step.
+def clip_from_sumsq(S: float, max_norm: float) -> Tuple[float, float, bool]:
+    """(norm, coef, bad) of the definition from an fp32 sum of squares S, in fp32 arithmetic (sqrt and
+    the quotient correctly rounded, as __fsqrt_rn / __fdiv_rn are): exactly what clip_finalize
+    derives from its own S."""
+    if not max_norm > 0:
+        raise ValueError("max_norm must be > 0 (inf: measure only)")
+    s = torch.tensor(float(S), dtype=torch.float32)
+    norm = torch.sqrt(s)
+    if not bool(torch.isfinite(norm)):
+        return float(norm), 0.0, True
+    c = torch.tensor(float(max_norm), dtype=torch.float32)
+    coef = 1.0 if bool(norm <= c) else float(c / norm)
+    return float(norm), coef, False
+
+
+def clip_coef_ref(g: torch.Tensor, gscale: float, max_norm: float, oracle: bool = False):
+    """(S, norm, coef, bad) of gradient ``g`` (any shape, fp32). fp32 composite: S summed by
+    torch in fp32; ``oracle``: S in fp64 from the fp32-rounded x_i (then norm and coef from
+    fl32(S) as the definition says)."""
+    x = g.detach().reshape(-1).to(torch.float32) * torch.tensor(float(gscale), dtype=torch.float32, device=g.device)
+    if oracle:
+        x = x.to(torch.float64)
+    S = float((x * x).sum().to(torch.float32)) if x.numel() else 0.0
+    norm, coef, bad = clip_from_sumsq(S, max_norm)
+    return S, norm, coef, bad
+
+
+def clipped_adam_ref(p, g, m, v, ema, p16, lr_t: float, b1: float, b2: float, eps: float, gscale: float,
+                     coef: Optional[float], keep: float, oracle: bool = False):
+    """One Adam (TF epsilon-hat) + EMA update of flat arrays with the gradient scaled by ``coef``
+    (None: unclipped; the caller skips a bad step).
+
+    fp32 composite (default): in place on p, m, v (and ema, p16 when given), the op sequence of the
+    unclipped CPU update with g' = (g gscale) coef in front. ``oracle``: nothing is modified; returns
+    fp64 {p, m, v, ema} computed from the fp32-rounded g' (the kernel's operand)."""
+    gj = g * gscale
+    if coef is not None:
+        gj = gj * coef
+    if oracle:
+        gj, p0, m0, v0 = gj.to(torch.float64), p.to(torch.float64), m.to(torch.float64), v.to(torch.float64)
+        m1 = b1 * m0 + (1 - b1) * gj
+        v1 = b2 * v0 + (1 - b2) * gj * gj
+        p1 = p0 - lr_t * m1 / (v1.sqrt() + eps)
+        out = dict(p=p1, m=m1, v=v1)
+        if ema is not None:
+            out["ema"] = p1 + keep * (ema.to(torch.float64) - p1)
+        return out
+    m.mul_(b1).add_(gj, alpha=1 - b1)
+    v.mul_(b2).addcmul_(gj, gj, value=1 - b2)
+    p.sub_(lr_t * m / (v.sqrt() + eps))
+    if ema is not None:
+        ema.copy_(p + keep * (ema - p))
+    if p16 is not None:
+        p16.copy_(p)
+    return None

@@ -192,8 +192,12 @@ def main(argv=None) -> int:
                       world_size=ctx.world_size, bucket_mb=args.bucket_mb,
                       allreduce_bf16=args.allreduce_dtype == "bf16", nan_policy=args.nan_policy,
                       step_graphs={"auto": "auto", "on": True, "off": False}[args.step_graphs],
-                      defer_update=True, dp_graphs=args.dp_step_graphs)
+                      defer_update=True, dp_graphs=args.dp_step_graphs, max_grad_norm=args.max_grad_norm)
     trainer.first_utt = ctx.rank * args.batch_size
+    # --max_grad_norm: a training hyper-parameter like --rnn_dropout (not restored from the
+    # parameter json, never read by evaluation)
+    if ctx.is_main and trainer.opt.clip:
+        print("max_grad_norm: %g" % args.max_grad_norm)
     if ctx.is_main and model.rnn_dropout_thr > 0:
         print("rnn_dropout:  p=%g (%d/65536), %s" % (args.rnn_dropout, model.rnn_dropout_thr, args.rnn_dropout_mode))
     # --specaug: masks and warp drawn per (seed, global step, global utterance index), so a
@@ -330,6 +334,8 @@ def main(argv=None) -> int:
                 audio_hist.append(audio_since / max(1e-9, now - t_last))
             t_last, steps_since, audio_since = now, 0, 0.0
             ema = trainer.update_loss_ema(lv)
+            # the host waits here anyway: the last measured step's norm and the clipping counters
+            clip = trainer.opt.clip_stats() if trainer.opt.clip else None
             if do_log and ctx.is_main and durations:
                 sec_batch = float(np.mean(durations))
                 ex_sec = args.batch_size * ctx.world_size / sec_batch
@@ -341,8 +347,15 @@ def main(argv=None) -> int:
                 else:
                     print("%s: step %d, loss = %.2f (%.1f examples/sec; %.3f sec/batch; %.1f audio-sec/sec)"
                           % (datetime.now(), step, lv, ex_sec, sec_batch, aps), flush=True)
+                if clip is not None:
+                    print("    grad_norm = %.4g, clip_coef = %.4g (clipped %d, skipped %d of %d steps)"
+                          % (clip["grad_norm"], clip["clip_coef"], clip["clipped_steps"], clip["skipped_steps"],
+                             clip["steps"]), flush=True)
             if ctx.is_main:
                 rec = dict(loss=lv, loss_ema=ema, lr=trainer.lr)
+                if clip is not None:
+                    rec.update(grad_norm=clip["grad_norm"], clip_coef=clip["clip_coef"],
+                               clipped_steps=clip["clipped_steps"], skipped_steps=clip["skipped_steps"])
                 if step_ms:
                     ms = np.asarray(step_ms)
                     rec.update(step_ms_p50=round(float(np.percentile(ms, 50)), 4),

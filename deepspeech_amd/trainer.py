@@ -13,6 +13,8 @@ MI355X step:
   loss.backward()                         RCCL bucket all-reduces launch from grad hooks
   bucketer.finish()                       wait for the in-flight buckets
   optimizer.step()                        fused Adam + EMA, one kernel over the arena
+                                          (max_grad_norm: two norm kernels first, then the
+                                          clipped update reading their device coefficient)
 No host synchronisation happens inside the step; the loss is returned as a device tensor.
 """
 from __future__ import annotations
@@ -129,7 +131,7 @@ class Trainer:
                  world_size: int = 1, bucket_mb: float = 32.0, allreduce_bf16: bool = False,
                  nan_policy: str = "abort", collapse_repeated: bool = False, force_buckets: bool = False,
                  step_graphs=False, graph_warmup: int = 2, bucket_split_after=(), defer_update: bool = False,
-                 dp_graphs: bool = False):
+                 dp_graphs: bool = False, max_grad_norm: float = 0.0):
         self.model = model
         # data parallel: capture the bucketed step too (RCCL all-reduces and the per-bucket
         # optimizer ranges inside the shape's graph); opt-in, see graphs_active()
@@ -143,7 +145,10 @@ class Trainer:
         self._seed = {}            # (device, dtype) -> device scalar 1.0 (backward seed)
         # bf16 compute shadows of the weights only for the HIP engine (fused ops read them)
         self.arena = ParamArena(model, bf16_shadow=(model.engine == "hip"))
-        self.opt = FusedAdamEMA(self.arena, lr=lr_schedule.initial_lr, ema_decay=moving_avg_decay)
+        # max_grad_norm = C > 0: clip the global gradient norm at C (inf: measure only); the step
+        # then updates nothing before the norm of the whole arena is known (see _body)
+        self.opt = FusedAdamEMA(self.arena, lr=lr_schedule.initial_lr, ema_decay=moving_avg_decay,
+                                max_grad_norm=max_grad_norm)
         self.lr_schedule = lr_schedule
         self.world = world_size
         self.bucketer = GradBucketer(self.arena, bucket_mb=bucket_mb, compress_bf16=allreduce_bf16,
@@ -418,7 +423,7 @@ class Trainer:
         gradients, bf16 shadows, Adam moments, EMA): a replay after any of them was re-allocated
         would write freed memory."""
         ts = (self.arena.flat, self.arena.grad, getattr(self.arena, "p16", None), self.opt.m, self.opt.v,
-              self.opt.ema)
+              self.opt.ema, self.opt.clip_state)
         return tuple(t.data_ptr() if t is not None else 0 for t in ts)
 
     def _replay(self, g: "_StepGraph", batch: Dict[str, torch.Tensor], width: int, lr_t: float,
@@ -518,7 +523,12 @@ class Trainer:
         if one is None:
             one = self._seed[(loss.device, loss.dtype)] = torch.ones((), device=loss.device, dtype=loss.dtype)
         gscale = 1.0 / self.world
-        per_bucket = self.bucketer.enabled and self.nan_policy != "skip" and self.per_bucket_update
+        # gradient-norm clipping: the coefficient is known only once every gradient is final (and
+        # reduced), so nothing below updates an element before that: no per-bucket optimizer, no
+        # early ranges beside the backward, no dU GEMM carried into the next step (it would write
+        # a gradient after the norm was taken). What survives is the carried update (below).
+        clip = self.opt.clip
+        per_bucket = self.bucketer.enabled and self.nan_policy != "skip" and self.per_bucket_update and not clip
         # (sequences of >= _PARTIAL_MIN_T recurrence steps only: beside a short recurrence the
         # carried ranges, capped to its idle CUs, outlast it and the projections wait for them)
         dp_carry = (per_bucket and self.defer_update and self.arena.flat.is_cuda and self._layer_first and
@@ -534,7 +544,7 @@ class Trainer:
             up = self.upper_range(1) if dp_carry else None
             self.bucketer.set_optimizer(lambda lo, hi: self.opt.apply_range(lo, hi, lr_t, keep, gscale),
                                         carry_hi=up[0] if up else 0)
-        early = (not per_bucket and self.nan_policy != "skip" and self._early_split > 0 and lazy and
+        early = (not per_bucket and not clip and self.nan_policy != "skip" and self._early_split > 0 and lazy and
                  self.arena.wgrad.grouped and self.arena.wgrad.defer_input)
         carry = early and self.defer_update and not torch.cuda.is_current_stream_capturing()
         carried = [0]
@@ -583,6 +593,25 @@ class Trainer:
                 self.opt.apply_range(lo, self.arena.numel, lr_t, keep, gscale)
             if carried[0] > 0:
                 self._carry_update(carried[0], lr_t, keep, gscale, carried_du)
+        elif clip:
+            # every gradient is final here (weight-gradient streams joined, unwritten slices zeroed,
+            # buckets reduced: ranks hold bitwise equal gradients and derive the same coefficient
+            # without a collective). The previous step's carried chunks, which read the state this
+            # overwrites, were settled right after the forward.
+            self.opt.measure_norm(gscale)
+            if self.nan_policy == "skip":
+                self.last_skip = self.opt.clip_bad_flag()       # the one pass over the gradients
+            up = None
+            if (self.defer_update and lazy and self.arena.flat.is_cuda and not self.bucketer.enabled
+                    and not torch.cuda.is_current_stream_capturing()):
+                up = self.upper_range(1)
+            with TR.phase(TR.EMA):
+                # single device, defer_update: the conv front-end's and layer 0's range now, the FC
+                # head and layers >= 1 as chunks beside the next forward's recurrences (no dUs),
+                # reading the same coefficient and bad flag
+                self.opt.apply_range(up[0] if up else 0, self.arena.numel, lr_t, keep, gscale)
+            if up:
+                self._carry_update(up[0], lr_t, keep, gscale)
         elif not per_bucket:
             skip = None
             if self.nan_policy == "skip":
