@@ -192,7 +192,7 @@ def main(argv=None) -> int:
     from . import config as C
     from .data.synthetic import to_device
     from .models import DeepSpeech2
-    from .test import NUM_EXAMPLES, build_eval_data
+    from .test import NUM_EXAMPLES, build_eval_data, eval_front_end
     from .utils import checkpoint as CK
 
     pre = argparse.ArgumentParser(add_help=False)
@@ -213,11 +213,14 @@ def main(argv=None) -> int:
     data = build_eval_data(args)
     n = args.num_examples or NUM_EXAMPLES.get(args.eval_data, 2048)
     aligner = Aligner(model)
+    front = eval_front_end(args, data, dev)       # an audio store is featurized per batch, unaugmented
     done = bad = 0
     with open(own.out, "w") as f:
         for _ in range(int(math.ceil(n / args.batch_size))):
             hb = data.next()
             b = to_device(hb, dev)
+            if front is not None:
+                b = front(b)
             ids = [hb.labels[i, : hb.label_lens[i]].tolist() for i in range(len(hb.label_lens))]
             for i, u in enumerate(aligner.align(b["feats"], b["seq_lens"], ids)):
                 f.write(json.dumps({

@@ -27,12 +27,12 @@ RESUME_KEYS = (
     "num_hidden", "num_rnn_layers", "rnn_type", "num_filters", "use_fp16",
     "temporal_stride", "initial_lr", "engine", "nchw",
     # extensions
-    "cell", "stack_fix", "seq_bn", "dtype", "ctc_collapse_repeated", "lookahead",
+    "cell", "stack_fix", "seq_bn", "dtype", "ctc_collapse_repeated", "lookahead", "audio_features",
 )
 EVAL_KEYS = (
     "num_hidden", "num_rnn_layers", "rnn_type", "num_filters", "use_fp16",
     "moving_avg_decay", "nchw",
-    "cell", "stack_fix", "seq_bn", "ctc_collapse_repeated", "lookahead",
+    "cell", "stack_fix", "seq_bn", "ctc_collapse_repeated", "lookahead", "audio_features",
 )
 
 
@@ -127,6 +127,17 @@ def build_train_parser() -> argparse.ArgumentParser:
                    help="SpecAugment on the training batches (ops/specaug.py): a preset (ld, ls) or a spec "
                         "such as F=27,nF=2,T=100,nT=2,p=0.2,W=0,fill=mean; empty = off. A training "
                         "hyper-parameter: a resume may change it, evaluation never augments")
+    p.add_argument("--audio_features", type=str, default="mfcc", choices=["mfcc", "spectrogram"],
+                   help="feature kind computed per step from an audio store (preprocess --store audio) or "
+                        "--dummy_audio (data/audio_batch.py); kept in deepSpeech_parameters.json for evaluation. "
+                        "A store of feature frames ignores it")
+    p.add_argument("--wave_aug", type=str, default="",
+                   help="additive noise on the training waveforms (ops/waveaug.py), before the featurizer: a spec "
+                        "such as noise=PATH|synthetic,p=0.4,snr=10:30; empty = off. Needs audio batches. A training "
+                        "hyper-parameter: a resume may change it, evaluation never augments")
+    p.add_argument("--dummy_audio", type=str2bool, default=False,
+                   help="--dummy True: serve seeded pseudo-audio rows [N, T + 1, 160] instead of frames, "
+                        "featurized per step like an audio store")
     p.add_argument("--rnn_dropout", type=float, default=0.0,
                    help="dropout probability on what recurrent layer i hands to layer i+1 (ops/dropout.py; the "
                         "top layer's output is not dropped), 0 = off. A training hyper-parameter: a resume "

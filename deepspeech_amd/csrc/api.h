@@ -372,4 +372,26 @@ int ds2_resample(const void* x, int in_i16, long long row_stride, int S, int B, 
                  int L, int M, int K, int in_off, int ph0, int n_out, int to_end, float* out, int* out_lens,
                  hipStream_t st);
 
+// ---- waveaug.hip -------------------------------------------------------------------------
+// Additive noise at a random SNR on the waveform: x fp32 / int16 [B, S] contiguous and 16-byte
+// aligned (S % 8 == 0, 8 <= S < 2^30, B <= 65535), lens int32 [B] or null, bank = data fp32
+// [Ntot < 2^31] with start, length int32 [C], plan int32 [B, 4] = (on, clip, off, snr_cdb), part
+// fp32 [B, ceil(S / ds2_waveaug_segment()), 2], energy fp64 [B, 2] = (Ex, En), coef fp32 [B], out
+// fp32 [B, S]. The plan kernel draws from Philox4x32-10 with key seed and counter (0, first_utt
+// + b, step_lo, 0x40000000 | step_hi & 0x3fffffff) and takes any S >= 1. Bank and plan words are
+// clamped into the bank on the device. -120: shape outside the contract, -121: policy outside
+// its range (p_ppm <= 1000000, |snr| <= 2^20 centi-dB, lo <= hi), -122: misaligned.
+int ds2_waveaug_segment();
+int ds2_waveaug_plan(const int* lens, const int* length, int* plan, int B, int S, int C, int p_ppm, int snr_lo_cdb,
+                     int snr_hi_cdb, unsigned seed_lo, unsigned seed_hi, unsigned step_lo, unsigned step_hi,
+                     unsigned first_utt, hipStream_t st);
+int ds2_waveaug_energy(const void* x, int in_i16, const int* lens, const int* plan, const float* data,
+                       const int* start, const int* length, int C, long long Ntot, float* part, int B, int S,
+                       hipStream_t st);
+int ds2_waveaug_coef(const int* lens, const int* plan, const float* part, double* energy, float* coef, int B, int S,
+                     hipStream_t st);
+int ds2_waveaug_apply(const void* x, int in_i16, const int* lens, const int* plan, const float* coef,
+                      const float* data, const int* start, const int* length, int C, long long Ntot, float* out, int B,
+                      int S, hipStream_t st);
+
 }  // extern "C"

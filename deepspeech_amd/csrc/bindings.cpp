@@ -1312,6 +1312,95 @@ void resample(at::Tensor pcm, OptT lens, at::Tensor h, int64_t L, int64_t M, int
                            op.stream()));
 }
 
+// --------------------------------------------------------------------------- noise augmentation (csrc/waveaug.hip)
+// x fp32 or int16 [B, S] (S % 8 == 0, 16-byte aligned), optional lens int32 [B], plan int32 [B, 4] =
+// (on, clip, off, snr_cdb); the bank: data fp32 [Ntot], start and length int32 [C]
+struct Wave {
+  const void* x;
+  int i16;
+  int B, S;
+  const int* lens;
+};
+Wave waveaug_x(const Op& op, const at::Tensor& x, const OptT& lens) {
+  op.dims(x, "x", 2, "B, S");
+  TORCH_CHECK(x.scalar_type() == at::kShort || x.scalar_type() == at::kFloat, op.op, ": x must be float32 or int16");
+  TORCH_CHECK(x.size(0) >= 1 && x.size(0) <= 65535 && x.size(1) >= 8 && x.size(1) < (1LL << 30) && x.size(1) % 8 == 0,
+              op.op, ": x [B, S] with B <= 65535, 8 <= S < 2^30, S % 8 == 0, got ", x.sizes());
+  return {op.raw(x, "x", x.scalar_type(), "B, S", whole(x), 16), x.scalar_type() == at::kShort ? 1 : 0, (int)x.size(0),
+          (int)x.size(1), op.lens(lens, "lens", x.size(0))};
+}
+int* waveaug_plan_arg(const Op& op, const at::Tensor& plan, int64_t B) {
+  return op.i32(plan, "plan", "B, 4", exactly(4 * B), 16);
+}
+struct NoiseBank {
+  const float* data;
+  const int *start, *length;
+  int C;
+  long long Ntot;
+};
+NoiseBank waveaug_bank(const Op& op, const at::Tensor& data, const at::Tensor& start, const at::Tensor& length) {
+  const int64_t C = length.numel(), Ntot = data.numel();
+  TORCH_CHECK(C >= 1 && C < (1LL << 31) && Ntot >= 1 && Ntot < (1LL << 31), op.op,
+              ": a bank of C >= 1 clips and 1 <= Ntot < 2^31 samples");
+  return {op.f32(data, "data", "Ntot", whole(data)), op.i32(start, "start", "C", exactly(C)),
+          op.i32(length, "length", "C", whole(length)), (int)C, (long long)Ntot};
+}
+int64_t waveaug_segments(int64_t S) { return (S + ds2_waveaug_segment() - 1) / ds2_waveaug_segment(); }
+
+// seed, step and first_utt come as 32-bit words; p in parts per million, the SNR range in centi-dB
+void waveaug_plan(OptT lens, at::Tensor length, at::Tensor plan, int64_t S, int64_t p_ppm, int64_t snr_lo_cdb,
+                  int64_t snr_hi_cdb, int64_t seed_lo, int64_t seed_hi, int64_t step_lo, int64_t step_hi,
+                  int64_t first_utt) {
+  const Op op{"waveaug.plan"};
+  op.dims(plan, "plan", 2, "B, 4");
+  const int64_t B = plan.size(0), C = length.numel();
+  TORCH_CHECK(B >= 1 && B < (1LL << 31) && S >= 1 && S < (1LL << 31) && C >= 1 && C < (1LL << 31), op.op,
+              ": B, S, C in [1, 2^31)");
+  TORCH_CHECK(p_ppm >= 0 && p_ppm <= 1000000 && snr_lo_cdb >= -(1 << 20) && snr_hi_cdb <= (1 << 20) &&
+                  snr_lo_cdb <= snr_hi_cdb,
+              op.op, ": policy value out of range");
+  op.launched(ds2_waveaug_plan(op.lens(lens, "lens", B), op.i32(length, "length", "C", whole(length)),
+                               waveaug_plan_arg(op, plan, B), (int)B, (int)S, (int)C, (int)p_ppm,
+                               (int)snr_lo_cdb, (int)snr_hi_cdb, op.word(seed_lo, "seed_lo"), op.word(seed_hi, "seed_hi"),
+                               op.word(step_lo, "step_lo"), op.word(step_hi, "step_hi"), op.word(first_utt, "first_utt"),
+                               op.stream()));
+}
+
+// part fp32 [B, segments of S, 2] = (sum x^2, sum z^2) per segment; segments at or past a row's length are not written
+void waveaug_energy(at::Tensor x, OptT lens, at::Tensor plan, at::Tensor data, at::Tensor start, at::Tensor length,
+                    at::Tensor part) {
+  const Op op{"waveaug.energy"};
+  const Wave w = waveaug_x(op, x, lens);
+  const NoiseBank k = waveaug_bank(op, data, start, length);
+  op.launched(ds2_waveaug_energy(w.x, w.i16, w.lens, waveaug_plan_arg(op, plan, w.B), k.data, k.start, k.length, k.C,
+                                 k.Ntot, op.f32(part, "part", "B, segments, 2", exactly(2 * w.B * waveaug_segments(w.S))),
+                                 w.B, w.S, op.stream()));
+}
+
+// energy fp64 [B, 2] = (Ex, En), the partials added in fp64; coef fp32 [B] = k (0 where the plan is off)
+void waveaug_coef(OptT lens, at::Tensor plan, at::Tensor part, at::Tensor energy, at::Tensor coef, int64_t S) {
+  const Op op{"waveaug.coef"};
+  op.dims(plan, "plan", 2, "B, 4");
+  const int64_t B = plan.size(0);
+  TORCH_CHECK(B >= 1 && B <= 65535 && S >= 8 && S < (1LL << 30) && S % 8 == 0, op.op,
+              ": B <= 65535, 8 <= S < 2^30, S % 8 == 0");
+  op.launched(ds2_waveaug_coef(op.lens(lens, "lens", B), waveaug_plan_arg(op, plan, B),
+                               op.f32(part, "part", "B, segments, 2", exactly(2 * B * waveaug_segments(S))),
+                               static_cast<double*>(op.raw(energy, "energy", at::kDouble, "B, 2", exactly(2 * B))),
+                               op.f32(coef, "coef", "B", exactly(B)), (int)B, (int)S, op.stream()));
+}
+
+// out fp32 [B, S] = x + coef * noise under the plan; rows that are off are copied, the tail past lens is +0
+void waveaug_apply(at::Tensor x, OptT lens, at::Tensor plan, at::Tensor coef, at::Tensor data, at::Tensor start,
+                   at::Tensor length, at::Tensor out) {
+  const Op op{"waveaug.apply"};
+  const Wave w = waveaug_x(op, x, lens);
+  const NoiseBank k = waveaug_bank(op, data, start, length);
+  op.launched(ds2_waveaug_apply(w.x, w.i16, w.lens, waveaug_plan_arg(op, plan, w.B), op.f32(coef, "coef", "B", exactly(w.B)),
+                                k.data, k.start, k.length, k.C, k.Ntot,
+                                op.f32(out, "out", "B, S", exactly((int64_t)w.B * w.S), 16), w.B, w.S, op.stream()));
+}
+
 // --------------------------------------------------------------------------- summaries (csrc/stats.hip)
 // counts int32 [hist_nbucket]; part fp32 [hist_blocks(n), 6 or more]
 void hist_stats(at::Tensor x, at::Tensor counts, at::Tensor part) {
@@ -1496,5 +1585,17 @@ PYBIND11_MODULE(_C, m) {
   m.def("hist_blocks", [](int64_t n) { return ds2_hist_blocks(n); });
   m.def("nonfinite_watch", &nonfinite_watch);
   m.def("spin", &spin);
+  // csrc/waveaug.hip; checked like the entries above by tests/test_waveaug_bindings.py
+  auto wa = m.def_submodule("waveaug", "additive-noise augmentation of waveforms (csrc/waveaug.hip)");
+  wa.def("plan", &waveaug_plan, py::arg("lens"), py::arg("length"), py::arg("plan"), py::arg("S"), py::arg("p_ppm"),
+         py::arg("snr_lo_cdb"), py::arg("snr_hi_cdb"), py::arg("seed_lo"), py::arg("seed_hi"), py::arg("step_lo"),
+         py::arg("step_hi"), py::arg("first_utt"));
+  wa.def("energy", &waveaug_energy, py::arg("x"), py::arg("lens"), py::arg("plan"), py::arg("data"), py::arg("start"),
+         py::arg("length"), py::arg("part"));
+  wa.def("coef", &waveaug_coef, py::arg("lens"), py::arg("plan"), py::arg("part"), py::arg("energy"), py::arg("coef"),
+         py::arg("S"));
+  wa.def("apply", &waveaug_apply, py::arg("x"), py::arg("lens"), py::arg("plan"), py::arg("coef"), py::arg("data"),
+         py::arg("start"), py::arg("length"), py::arg("out"));
+  wa.def("segment", []() { return ds2_waveaug_segment(); });
 }
 

@@ -2,7 +2,11 @@
 
   python -m deepspeech_amd.data.preprocess --audio_path ../data/LibriSpeech/audio \
          --out_dir ../data/LibriSpeech/processed [--features mfcc|spectrogram] [--tfrecords]
-         [--featurizer numpy|gpu] [--resample_to RATE]
+         [--featurizer numpy|gpu] [--resample_to RATE] [--store features|audio]
+
+``--store audio`` writes the samples themselves (an audio store, data/store.py: rows of one
+160-sample hop at 16 kHz) instead of feature frames; training then featurizes per step on the
+GPU, which is what waveform augmentation (train --wave_aug) needs.
 
 ``--featurizer numpy`` (default) runs data/featurizer.py one file at a time; ``gpu`` batches
 about 64 utterances per call through the HIP featurizer (ops/featurize.py) and feeds the same
@@ -118,12 +122,46 @@ def _gpu_features(items: List[Tuple[str, str]], features: str, resample_to: int 
     return utts
 
 
+def _audio_partition(part_dir: str, out_prefix: str, featurizer: str, resample_to: int) -> Dict[str, int]:
+    """An audio store (data/store.py): the 16 kHz samples themselves in rows of one hop, sorted by
+    length; the training and evaluation drivers featurize them per batch."""
+    from .store import AUDIO_RATE
+    utts = []
+    for path, text in scan_partition(part_dir):
+        audio, sr = read_audio(path)
+        if resample_to and sr != resample_to:
+            if featurizer == "gpu":
+                from ..ops.resample import Resampler
+                y, n = Resampler(sr, resample_to)(audio.astype(np.float32)[None, :])
+                audio = y[0, : int(n[0])].cpu().numpy()
+            else:
+                from ..ops.reference import resample_ref
+                audio = resample_ref(audio, sr, resample_to)
+            sr = resample_to
+        if sr != AUDIO_RATE:
+            raise ValueError("%s is at %d Hz and an audio store holds %d Hz: pass --resample_to %d"
+                             % (path, sr, AUDIO_RATE, AUDIO_RATE))
+        utts.append((np.asarray(audio, np.float32), encode_transcript(text), text))
+    utts.sort(key=lambda u: u[0].shape[0])                 # SortaGrad order
+    w = StoreWriter(out_prefix, 160, kind="audio")
+    for audio, lab, text in utts:
+        w.add_audio(audio, lab, text)
+    w.close()
+    return {"utterances": len(utts), "rows": int(sum(w.lengths))}
+
+
 def process_partition(part_dir: str, out_prefix: str, features: str = "mfcc",
                       tfrecord_dir: str = "", is_train: bool = False, min_bin: int = 20,
-                      featurizer: str = "numpy", resample_to: int = 0) -> Dict[str, int]:
+                      featurizer: str = "numpy", resample_to: int = 0, store: str = "features") -> Dict[str, int]:
     if featurizer not in ("numpy", "gpu"):
         raise ValueError("featurizer must be 'numpy' or 'gpu', not %r" % (featurizer,))
+    if store not in ("features", "audio"):
+        raise ValueError("store must be 'features' or 'audio', not %r" % (store,))
     resample_to = int(resample_to)
+    if store == "audio":
+        if tfrecord_dir:
+            raise ValueError("--tfrecords holds feature frames; an audio store has no TFRecord form")
+        return _audio_partition(part_dir, out_prefix, featurizer, resample_to)
     utts = []
     if featurizer == "gpu":
         utts = _gpu_features(scan_partition(part_dir), features, resample_to)
@@ -169,6 +207,9 @@ def main(argv=None):
                     help="numpy: data/featurizer.py, one file at a time; gpu: batched HIP kernels (ops/featurize.py)")
     ap.add_argument("--resample_to", type=int, default=0, metavar="RATE",
                     help="resample every file to RATE Hz before featurizing (0: featurize at the file's rate)")
+    ap.add_argument("--store", default="features", choices=["features", "audio"],
+                    help="features: feature frames [frames, 161]; audio: the 16 kHz samples in rows of 160 "
+                         "(--features is then chosen at training time: train --audio_features)")
     a = ap.parse_args(argv)
     for part in sorted(glob.glob(os.path.join(a.audio_path, "*"))):
         if not os.path.isdir(part):
@@ -176,7 +217,7 @@ def main(argv=None):
         name = os.path.basename(part)
         stats = process_partition(part, os.path.join(a.out_dir, name), a.features,
                                   a.out_dir if a.tfrecords else "", is_train=name.startswith("train"),
-                                  featurizer=a.featurizer, resample_to=a.resample_to)
+                                  featurizer=a.featurizer, resample_to=a.resample_to, store=a.store)
         print(name, stats)
 
 

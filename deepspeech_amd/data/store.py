@@ -5,6 +5,12 @@ Store layout (``<prefix>`` = e.g. ``processed/train-clean-100``):
   <prefix>.index.npz offsets[int64], lengths[int32], labels[int32 flat],
                      label_offsets[int64], label_lens[int32], (optional) transcripts
 
+An audio store is the same layout with rows that are hops of raw samples instead of feature
+frames: ``.feats`` holds float32 [total_rows, 160], each utterance zero-padded to a whole number
+of 160-sample rows (at most 159 zeros, under 10 ms), and the index also holds ``kind = "audio"``
+and ``rate = 16000``; ``lengths`` are rows. The featurizer (data/audio_batch.py) turns ``rows``
+rows into ``rows - 1`` frames, so batches are planned with ``min_frames() + 1``.
+
 It replaces the reference's per-length-bin TFRecord files (src/preprocess_LibriSpeech.py:
 143-176, read back by src/deepSpeech_input.py) with one mmap-able file per partition; the
 length bucketing happens at batch-planning time instead (runtime/loader.cpp). TFRecord
@@ -23,8 +29,17 @@ from .. import FREQ_BINS
 from ..config import get_rnn_seqlen_py
 
 
+AUDIO_HOP = 160          # samples per row of an audio store: one 10 ms hop at 16 kHz
+AUDIO_RATE = 16000
+
+
 class StoreWriter:
-    def __init__(self, prefix: str, freq: int = FREQ_BINS):
+    def __init__(self, prefix: str, freq: int = FREQ_BINS, kind: str = "features"):
+        if kind not in ("features", "audio"):
+            raise ValueError("store kind must be 'features' or 'audio', not %r" % (kind,))
+        if kind == "audio" and freq != AUDIO_HOP:
+            raise ValueError("an audio store has rows of %d samples" % AUDIO_HOP)
+        self.kind = kind
         os.makedirs(os.path.dirname(prefix) or ".", exist_ok=True)
         self.prefix = prefix
         self.freq = freq
@@ -45,15 +60,25 @@ class StoreWriter:
         self.transcripts.append(transcript)
         self._frames += feats.shape[0]
 
+    def add_audio(self, samples: np.ndarray, labels: Sequence[int], transcript: str = "") -> None:
+        """One utterance of an audio store: 1-D samples at 16 kHz, zero-padded to whole rows."""
+        assert self.kind == "audio"
+        samples = np.asarray(samples, dtype=np.float32).reshape(-1)
+        rows = max(1, -(-samples.shape[0] // AUDIO_HOP))
+        padded = np.zeros(rows * AUDIO_HOP, np.float32)
+        padded[: samples.shape[0]] = samples
+        self.add(padded.reshape(rows, AUDIO_HOP), labels, transcript)
+
     def close(self) -> str:
         self._f.close()
         lab_lens = np.array([len(l) for l in self.labels], np.int32)
         lab_off = np.concatenate([[0], np.cumsum(lab_lens)[:-1]]).astype(np.int64) if len(lab_lens) else np.zeros(0, np.int64)
+        extra = dict(kind=np.array("audio"), rate=np.int32(AUDIO_RATE)) if self.kind == "audio" else {}
         np.savez(self.prefix + ".index.npz",
                  offsets=np.array(self.offsets, np.int64), lengths=np.array(self.lengths, np.int32),
                  labels=np.concatenate(self.labels).astype(np.int32) if self.labels else np.zeros(0, np.int32),
                  label_offsets=lab_off, label_lens=lab_lens, freq=np.int32(self.freq),
-                 transcripts=np.array(self.transcripts))
+                 transcripts=np.array(self.transcripts), **extra)
         return self.prefix
 
 
@@ -66,12 +91,19 @@ class StoreIndex:
     label_offsets: np.ndarray
     label_lens: np.ndarray
     freq: int
+    kind: str = "features"       # "audio": rows are 160-sample hops of raw audio
+    rate: int = 0
 
     @staticmethod
     def load(prefix: str) -> "StoreIndex":
         z = np.load(prefix + ".index.npz", allow_pickle=False)
+        kind = str(z["kind"]) if "kind" in z.files else "features"
         return StoreIndex(prefix, z["offsets"], z["lengths"], z["labels"], z["label_offsets"],
-                          z["label_lens"], int(z["freq"]))
+                          z["label_lens"], int(z["freq"]), kind, int(z["rate"]) if "rate" in z.files else 0)
+
+    @property
+    def is_audio(self) -> bool:
+        return self.kind == "audio"
 
     def __len__(self) -> int:
         return int(len(self.lengths))
@@ -112,7 +144,8 @@ class StoreBatches:
         ix = self.index
         self.loader = self.N.BatchLoader(prefix + ".feats", ix.freq, ix.offsets, ix.lengths, ix.labels,
                                          ix.label_offsets, ix.label_lens, num_threads, 1)
-        self._min = ix.min_frames()
+        # an audio store's rows become rows - 1 frames
+        self._min = ix.min_frames() + 1 if ix.is_audio else ix.min_frames()
         self.epoch = 0
         self._queue: List[List[int]] = []
         self._submitted = 0

@@ -11,6 +11,11 @@ Two generators:
   per-utterance lengths inside one 100-frame bucket (like bucket_by_sequence_length,
   src/deepSpeech_input.py:53-60), label lengths at LibriSpeech's ~15 chars/s.
 
+With ``audio=True`` either serves seeded pseudo-audio instead of frames: ``[N, T + 1, 160]`` rows
+of one 160-sample hop each (what an audio store holds, data/store.py), ``seq_lens = T + 1`` rows,
+which the front end (data/audio_batch.py) featurizes into T frames; the frame counts and label
+lengths are drawn as for the frame feed.
+
 Both produce numpy batches generated off the timed path; :func:`to_device` moves one
 to pinned host memory and then to the GPU asynchronously.
 """
@@ -32,6 +37,7 @@ COUNTS = [30, 3, 3, 3, 14, 13, 9, 8, 5, 4, 3, 2, 2, 2, 1]
 LABEL_LENGTHS = [7, 17, 7, 48, 62, 78, 93, 107, 120, 134, 148, 163, 178, 193, 209]
 SCALE_FACTOR = 10
 EXTRA = 1000
+AUDIO_HOP = 160        # samples per row of an audio batch (data/store.py)
 CHARS_PER_SEC = 15.0   # LibriSpeech read speech ~ 14-16 characters / second
 
 
@@ -85,12 +91,14 @@ def feasible_label_len(frames: int, want: int, labels: Optional[np.ndarray] = No
 class DummyBucketWalk:
     """Replays the reference dummy epoch: buckets in ascending order of index."""
 
-    def __init__(self, batch_size: int, seed: int = 0, scale_factor: int = SCALE_FACTOR):
+    def __init__(self, batch_size: int, seed: int = 0, scale_factor: int = SCALE_FACTOR, audio: bool = False):
         self.batch_size = batch_size
         self.rng = np.random.default_rng(seed)
         self.scale = scale_factor
+        self.width = AUDIO_HOP if audio else FREQ_BINS
+        self.more = 1 if audio else 0           # rows past the frame count: T + 1 hops make T frames
         self.buffer = self.rng.standard_normal(
-            (batch_size * (UTT_LENGTHS[-1] + EXTRA), FREQ_BINS)).astype(np.float32)
+            (batch_size * (UTT_LENGTHS[-1] + self.more + EXTRA), self.width)).astype(np.float32)
         self._reset()
 
     def _reset(self) -> None:
@@ -124,12 +132,13 @@ class DummyBucketWalk:
         B = self.batch_size
         T = UTT_LENGTHS[i]
         start = int(self.rng.integers(0, EXTRA + B * (UTT_LENGTHS[-1] - T)))
-        feats = self.buffer[start: start + T * n].reshape(n, T, FREQ_BINS)
+        R = T + self.more
+        feats = self.buffer[start: start + R * n].reshape(n, R, self.width)
         label = random_labels(self.rng, 1, LABEL_LENGTHS[i])
         L = feasible_label_len(T, LABEL_LENGTHS[i], label[0])
         label = label[:, :L]
         labels = np.repeat(label, n, axis=0)     # reference replicates one label per batch
-        return Batch(feats=np.ascontiguousarray(feats), seq_lens=np.full(n, T, np.int32),
+        return Batch(feats=np.ascontiguousarray(feats), seq_lens=np.full(n, R, np.int32),
                      labels=labels, label_lens=np.full(n, L, np.int32))
 
     def __iter__(self) -> Iterator[Batch]:
@@ -142,13 +151,14 @@ class FixedShapeBatches:
 
     def __init__(self, batch_size: int, max_frames: int = 1000, bucket: int = 100,
                  seed: int = 0, pool: int = 4, chars_per_sec: float = CHARS_PER_SEC,
-                 variable_lengths: bool = True):
+                 variable_lengths: bool = True, audio: bool = False):
+        width, more = (AUDIO_HOP, 1) if audio else (FREQ_BINS, 0)
         self.batch_size = batch_size
         self.T = max_frames
         self.rng = np.random.default_rng(seed)
         self.batches: List[Batch] = []
         for _ in range(pool):
-            feats = self.rng.standard_normal((batch_size, max_frames, FREQ_BINS)).astype(np.float32)
+            feats = self.rng.standard_normal((batch_size, max_frames + more, width)).astype(np.float32)
             if variable_lengths:
                 lens = self.rng.integers(max(21 + 18, max_frames - bucket + 1), max_frames + 1,
                                          size=batch_size).astype(np.int32)
@@ -161,8 +171,8 @@ class FixedShapeBatches:
             labels = np.full((batch_size, int(L.max())), -1, np.int32)
             for b in range(batch_size):
                 labels[b, : L[b]] = rows[b][: L[b]]
-                feats[b, lens[b]:] = 0.0
-            self.batches.append(Batch(feats, lens, labels, L))
+                feats[b, lens[b] + more:] = 0.0
+            self.batches.append(Batch(feats, lens + more if more else lens, labels, L))
         self.i = 0
 
     def next(self) -> Batch:

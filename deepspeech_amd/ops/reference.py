@@ -673,3 +673,105 @@ def clipped_adam_ref(p, g, m, v, ema, p16, lr_t: float, b1: float, b2: float, ep
     if p16 is not None:
         p16.copy_(p)
     return None
+
+
+# ---------------------------------------------------------------------------- additive noise (ops/waveaug.py, csrc/waveaug.hip)
+# Definition shared by the kernels, the torch composite and the tests. x [B, S] fp32 or int16
+# (converted exactly, no 1/32768), n = clamp(lens[b], 0, S) (lens None: S), a bank of C clips
+# (data fp32 [Ntot], start / length int32 [C]), a policy (p_ppm, snr_lo_cdb, snr_hi_cdb):
+#   plan   (on, clip, off, snr_cdb) from one Philox4x32-10 block per utterance, key seed, counter
+#          (0, u, step & 0xffffffff, 0x40000000 | (step >> 32) & 0x3fffffff), u = first_utt + b;
+#          with U(w, m) = (w * m) >> 32: on = n > 0 and U(x0, 1000000) < p_ppm, clip = U(x1, C),
+#          off = U(x2, length[clip]), snr_cdb = snr_lo_cdb + U(x3, snr_hi_cdb - snr_lo_cdb + 1)
+#   z_i    data[start[clip] + (off + i) mod length[clip]]
+#   Ex, En sum over i < n of x_i^2 and z_i^2 (fp64 here)
+#   k      fl32(sqrt(Ex / (En 10^(snr_cdb / 1000)))), 0 when not on, Ex == 0, En == 0 or not finite
+#   y_i    fl32(x_i + fl32(k z_i)) for i < n when on, x_i (a bit copy) when not, +0 for i >= n
+WAVEAUG_STREAM = 0x40000000
+
+
+def waveaug_lens(lens, B: int, S: int) -> np.ndarray:
+    if lens is None:
+        return np.full(B, S, np.int64)
+    return np.clip(np.asarray(torch.as_tensor(lens).cpu()).astype(np.int64).reshape(-1), 0, S)
+
+
+def waveaug_plan_ref(lens, B: int, S: int, length, policy, seed: int, step: int, first_utt: int = 0) -> torch.Tensor:
+    """The plan [B, 4] int32 = (on, clip, off, snr_cdb) of utterances first_utt .. first_utt + B - 1
+    at ``step``, in exact integer arithmetic. ``length`` [C] are the bank's clip lengths, ``policy``
+    has p_ppm, snr_lo_cdb, snr_hi_cdb."""
+    n = waveaug_lens(lens, B, S)
+    length = np.asarray(torch.as_tensor(length).cpu()).astype(np.int64).reshape(-1)
+    u = (int(first_utt) + np.arange(B, dtype=np.uint64)) & np.uint64(0xffffffff)
+    x = philox4x32((np.uint64(0), u, np.uint64(step & 0xffffffff),
+                    np.uint64(WAVEAUG_STREAM | ((step >> 32) & 0x3fffffff))),
+                   (np.uint64(seed & 0xffffffff), np.uint64((seed >> 32) & 0xffffffff)))
+    x = [np.broadcast_to(w, (B,)).astype(np.uint64) for w in x]
+
+    def U(xw, m):
+        return ((xw * np.asarray(m, np.int64).astype(np.uint64)) >> np.uint64(32)).astype(np.int64)
+
+    plan = np.zeros((B, 4), np.int64)
+    plan[:, 0] = (n > 0) & (U(x[0], 1000000) < int(policy.p_ppm))
+    plan[:, 1] = U(x[1], length.shape[0])
+    plan[:, 2] = U(x[2], length[plan[:, 1]])
+    plan[:, 3] = int(policy.snr_lo_cdb) + U(x[3], int(policy.snr_hi_cdb) - int(policy.snr_lo_cdb) + 1)
+    return torch.from_numpy(plan.astype(np.int32))
+
+
+def waveaug_noise_ref(plan, data, start, length, S: int) -> torch.Tensor:
+    """z [B, S] fp32: each row's clip read as a loop from its offset."""
+    plan = np.asarray(torch.as_tensor(plan).cpu()).astype(np.int64)
+    data = np.asarray(torch.as_tensor(data).cpu())
+    start = np.asarray(torch.as_tensor(start).cpu()).astype(np.int64)
+    length = np.asarray(torch.as_tensor(length).cpu()).astype(np.int64)
+    clip = plan[:, 1]
+    idx = start[clip][:, None] + (plan[:, 2][:, None] + np.arange(S, dtype=np.int64)[None, :]) % length[clip][:, None]
+    return torch.from_numpy(np.ascontiguousarray(data[idx], np.float32))
+
+
+def waveaug_energy_ref(x, lens, z) -> torch.Tensor:
+    """fp64 [B, 2] = (Ex, En) over i < n."""
+    xv = np.asarray(torch.as_tensor(x).cpu()).astype(np.float64)
+    zv = np.asarray(torch.as_tensor(z).cpu()).astype(np.float64)
+    B, S = xv.shape
+    valid = np.arange(S)[None, :] < waveaug_lens(lens, B, S)[:, None]
+    e = np.stack([np.where(valid, xv * xv, 0.0).sum(1), np.where(valid, zv * zv, 0.0).sum(1)], 1)
+    return torch.from_numpy(e)
+
+
+def waveaug_coef_ref(plan, energy) -> torch.Tensor:
+    """fp32 [B]: k evaluated in fp64 and rounded once, 0 by selection."""
+    plan = np.asarray(torch.as_tensor(plan).cpu()).astype(np.int64)
+    e = np.asarray(torch.as_tensor(energy).cpu()).astype(np.float64)
+    with np.errstate(all="ignore"):
+        k = np.sqrt(e[:, 0] / (e[:, 1] * np.power(10.0, plan[:, 3] / 1000.0))).astype(np.float32)
+    ok = (plan[:, 0] != 0) & (e[:, 0] != 0) & (e[:, 1] != 0) & np.isfinite(k)
+    return torch.from_numpy(np.where(ok, k, np.float32(0)).astype(np.float32))
+
+
+def waveaug_mix_ref(x, lens, plan, z, coef) -> torch.Tensor:
+    """y fp32 [B, S] from a plan, its noise rows and coefficients: two roundings per sample."""
+    xv = np.asarray(torch.as_tensor(x).cpu())
+    if xv.dtype != np.float32:
+        xv = xv.astype(np.float32)                       # int16: exact
+    zv = np.asarray(torch.as_tensor(z).cpu()).astype(np.float32)
+    k = np.asarray(torch.as_tensor(coef).cpu()).astype(np.float32)
+    on = np.asarray(torch.as_tensor(plan).cpu())[:, 0] != 0
+    B, S = xv.shape
+    valid = np.arange(S)[None, :] < waveaug_lens(lens, B, S)[:, None]
+    with np.errstate(all="ignore"):
+        mixed = (xv + (k[:, None] * zv).astype(np.float32)).astype(np.float32)
+    y = np.where(on[:, None], mixed, xv)
+    return torch.from_numpy(np.where(valid, y, np.float32(0)).astype(np.float32))
+
+
+def waveaug_ref(x, lens, bank, policy, seed: int, step: int, first_utt: int = 0):
+    """(y, plan, energy, coef) of the definition; ``bank`` has data, start, length."""
+    x = torch.as_tensor(x)
+    B, S = x.shape
+    plan = waveaug_plan_ref(lens, B, S, bank.length, policy, seed, step, first_utt)
+    z = waveaug_noise_ref(plan, bank.data, bank.start, bank.length, S)
+    energy = waveaug_energy_ref(x, lens, z)
+    coef = waveaug_coef_ref(plan, energy)
+    return waveaug_mix_ref(x, lens, plan, z, coef), plan, energy, coef

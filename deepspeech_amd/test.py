@@ -95,15 +95,28 @@ def decode(logits: torch.Tensor, lens: torch.Tensor, decoder: str, beam_width: i
     return D.beam_decode(logits, lens, beam_width, BLANK, -10.0, lm=lm, lm_weight=lm_weight, label_bonus=label_bonus)
 
 
+def eval_front_end(args, data, dev):
+    """The audio front end (data/audio_batch.py) of an audio store, without augmentation and with
+    the feature kind of the checkpoint directory's parameter file; None for feature frames."""
+    index = getattr(data, "index", None)
+    if index is None or not index.is_audio:
+        return None
+    from .data.audio_batch import AudioFrontEnd
+    return AudioFrontEnd(getattr(args, "audio_features", "mfcc"), dev)
+
+
 def eval_once(model, args, data, num_iter: int, display: bool, lm=None, wer_out=None) -> float:
     """Mean CER in percent; with ``wer_out`` (a list) the corpus WER in percent is appended to it."""
     model.eval()
     cers = []
     werr = wref = 0
+    front = eval_front_end(args, data, model.fc_weight.device)
     with torch.no_grad():
         for step in range(num_iter):
             hb = data.next()
             b = to_device(hb, model.fc_weight.device)
+            if front is not None:
+                b = front(b)
             logits, lens = model(b["feats"], b["seq_lens"])
             preds = decode(logits, lens, args.decoder, args.beam_width, lm, getattr(args, "lm_weight", 1.0),
                            getattr(args, "label_bonus", 0.0))

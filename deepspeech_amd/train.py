@@ -65,9 +65,16 @@ def build_data(args, ctx, train_dir):
         if args.dummy_frames > 0:
             # fixed-length synthetic batches (bench.py's shape) instead of the reference's walk
             from .data.synthetic import FixedShapeBatches
-            src = FixedShapeBatches(args.batch_size, max_frames=args.dummy_frames, seed=args.seed + ctx.rank, pool=4)
+            if args.dummy_audio:
+                src = FixedShapeBatches(args.batch_size, max_frames=args.dummy_frames, seed=args.seed + ctx.rank, pool=4,
+                                        audio=True)
+            else:
+                src = FixedShapeBatches(args.batch_size, max_frames=args.dummy_frames, seed=args.seed + ctx.rank, pool=4)
             return src, 1000
-        src = DummyBucketWalk(args.batch_size, seed=args.seed + ctx.rank)
+        if args.dummy_audio:
+            src = DummyBucketWalk(args.batch_size, seed=args.seed + ctx.rank, audio=True)
+        else:
+            src = DummyBucketWalk(args.batch_size, seed=args.seed + ctx.rank)
         return src, src.steps_per_epoch()
     from .data.store import StoreBatches, find_partition_files, find_store, tfrecords_to_store
     if not args.data_dir:
@@ -85,6 +92,34 @@ def build_data(args, ctx, train_dir):
                        max_frames=args.max_frames, sortagrad_epochs=args.sortagrad_epochs if not args.shuffle else 0,
                        shuffle=True, seed=args.seed)
     return src, src.steps_per_epoch()
+
+
+def build_front_end(args, data, dev, is_main: bool = True):
+    """The per-step audio front end (data/audio_batch.py) of a source that serves raw audio (an
+    audio store, detected from its index, or --dummy_audio), else None. --wave_aug needs one."""
+    index = getattr(data, "index", None)
+    audio = bool(args.dummy_audio) if args.dummy else bool(index is not None and index.is_audio)
+    if not audio:
+        if args.wave_aug:
+            if hasattr(data, "close"):
+                data.close()
+            raise ValueError("--wave_aug acts on waveforms, and this run reads stored feature frames: write an "
+                             "audio store with `python -m deepspeech_amd.data.preprocess --store audio` "
+                             "(or use --dummy True --dummy_audio True)")
+        return None
+    from .data.audio_batch import AudioFrontEnd
+    wave_aug = None
+    if args.wave_aug:
+        # noise drawn per (seed, global step, global utterance index) like --specaug, on a Philox
+        # stream of its own
+        from .ops.waveaug import NoiseBank, WaveAugment, WaveAugPolicy
+        policy = WaveAugPolicy.parse(args.wave_aug)
+        wave_aug = WaveAugment(policy, NoiseBank.from_policy(policy, args.seed), args.seed)
+        if is_main:
+            print("wave_aug: ", policy, "(%d clips)" % len(wave_aug.bank))
+    if is_main:
+        print("audio_features: ", args.audio_features)
+    return AudioFrontEnd(args.audio_features, dev, wave_aug)
 
 
 def write_debug_reports(prof, model, args, dev) -> None:
@@ -188,6 +223,8 @@ def main(argv=None) -> int:
     if args.engine in ("mkldnn_rnn", "cudnn_rnn") and model.cell == "rnn_relu" and model.layout == "nchw":
         model.param_layout = "mkldnn"
     data, steps_per_epoch = build_data(args, ctx, args.train_dir)
+    # --wave_aug: a training hyper-parameter like --specaug (not restored, never read by evaluation)
+    front = build_front_end(args, data, dev, ctx.is_main)
     trainer = Trainer(model, lr_schedule_from_args(args, steps_per_epoch), args.moving_avg_decay,
                       world_size=ctx.world_size, bucket_mb=args.bucket_mb,
                       allreduce_bf16=args.allreduce_dtype == "bf16", nan_policy=args.nan_policy,
@@ -252,7 +289,8 @@ def main(argv=None) -> int:
             hb_ = data.next()
             return collapse_batch_labels(hb_) if args.ctc_collapse_repeated else hb_
     src = _Src()
-    if (aug is not None or model.rnn_dropout_thr > 0) and args.dummy and start > 0:
+    wave_on = front is not None and front.wave_aug is not None
+    if (aug is not None or wave_on or model.rnn_dropout_thr > 0) and args.dummy and start > 0:
         # an augmented synthetic run resumes its feed too (the generators are cheap to replay), so
         # its steps are those of the uninterrupted run: the same batch under the same masks
         for _ in range(start):
@@ -281,6 +319,9 @@ def main(argv=None) -> int:
             prof.__enter__()
         if batch is None:
             batch = to_device(hb, dev)
+        if front is not None:
+            # wave augmentation, featurize, then SpecAugment: all outside the step graphs
+            batch = front(batch, step, first_utt=ctx.rank * args.batch_size, training=True)
         if aug is not None:
             batch = dict(batch, feats=aug(batch["feats"], batch["seq_lens"], step,
                                           first_utt=ctx.rank * args.batch_size))
