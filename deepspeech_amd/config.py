@@ -135,6 +135,11 @@ def build_train_parser() -> argparse.ArgumentParser:
                    help="additive noise on the training waveforms (ops/waveaug.py), before the featurizer: a spec "
                         "such as noise=PATH|synthetic,p=0.4,snr=10:30; empty = off. Needs audio batches. A training "
                         "hyper-parameter: a resume may change it, evaluation never augments")
+    p.add_argument("--speed_perturb", type=str, default="",
+                   help="speed perturbation of the training waveforms (ops/speed.py), before --wave_aug and the "
+                        "featurizer: factors such as 0.9,1.0,1.1, one drawn per utterance and step; empty = off. "
+                        "Needs audio batches. A training hyper-parameter: a resume may change it, evaluation never "
+                        "augments")
     p.add_argument("--dummy_audio", type=str2bool, default=False,
                    help="--dummy True: serve seeded pseudo-audio rows [N, T + 1, 160] instead of frames, "
                         "featurized per step like an audio store")

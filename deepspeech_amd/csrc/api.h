@@ -394,4 +394,32 @@ int ds2_waveaug_apply(const void* x, int in_i16, const int* lens, const int* pla
                       const float* data, const int* start, const int* length, int C, long long Ntot, float* out, int B,
                       int S, hipStream_t st);
 
+// ---- speed.hip ---------------------------------------------------------------------------
+// Speed perturbation: every row of x fp32 / int16 [B, S] (contiguous, S < 2^30, B <= 65535) is
+// resampled by its own variant of a policy of V <= 8 distinct percents, or copied (100 %). The
+// policy travels by value: variant v with pct != 100 has L * pct == M * 100, K even, (L, M, K)
+// inside csrc/resample.hip's contract, and its table h[off .. off + L * K) in the coefficient
+// array (off % 4 == 0); a 100 % record has L = M = 1, K = 0, off = 0. plan int32 [B, 2] =
+// (pct, n_out); lens, min_out int32 [B] or null; max_out 0: none. The plan kernel draws variant
+// U(x0, V) from the Philox4x32-10 block with key seed and counter (1, first_utt + b, step_lo,
+// 0x40000000 | step_hi & 0x3fffffff) and falls back to (100, n) when n == 0 or the candidate
+// count ceil(n L / M) is below min_out[b] or above max_out. The apply kernel writes out fp32
+// [B, n_out] and out_lens int32 [B]; plan words are clamped on the device (an unknown percent
+// copies, a count stops at n_out). -130: shape outside the contract, -131: policy outside it,
+// -132: n_out below ds2_speed_out_width when the caller did not vouch for it.
+struct DS2SpeedTable {
+  int V;
+  int pct[8], L[8], M[8], K[8], off[8];
+};
+
+int ds2_speed_tile();
+int ds2_speed_supported(const DS2SpeedTable* t, long long h_words);
+long long ds2_speed_out_width(const DS2SpeedTable* t, long long S);   // worst case, a multiple of 160
+int ds2_speed_plan(const int* lens, const int* min_out, int* plan, int B, int S, int max_out, const DS2SpeedTable* t,
+                   unsigned seed_lo, unsigned seed_hi, unsigned step_lo, unsigned step_hi, unsigned first_utt,
+                   hipStream_t st);
+int ds2_speed_apply(const void* x, int in_i16, int B, int S, const int* lens, const int* plan, const float* h,
+                    long long h_words, const DS2SpeedTable* t, float* out, int n_out, int tight, int* out_lens,
+                    hipStream_t st);
+
 }  // extern "C"

@@ -1401,6 +1401,64 @@ void waveaug_apply(at::Tensor x, OptT lens, at::Tensor plan, at::Tensor coef, at
                                 op.f32(out, "out", "B, S", exactly((int64_t)w.B * w.S), 16), w.B, w.S, op.stream()));
 }
 
+// --------------------------------------------------------------------------- speed perturbation (csrc/speed.hip)
+// A policy crosses the boundary as 5 V integers, (pct, L, M, K, table offset) per variant; h fp32 holds the
+// variants' tables back to back; plan int32 [B, 2] = (pct, n_out)
+DS2SpeedTable speed_table(const Op& op, const std::vector<int64_t>& vtab, int64_t h_words) {
+  TORCH_CHECK(!vtab.empty() && vtab.size() % 5 == 0 && vtab.size() <= 40, op.op,
+              ": a policy is 5 V integers (pct, L, M, K, offset), 1 <= V <= 8, got ", vtab.size());
+  DS2SpeedTable t{};
+  t.V = (int)(vtab.size() / 5);
+  for (int v = 0; v < t.V; ++v) {
+    for (int i = 0; i < 5; ++i)
+      TORCH_CHECK(vtab[5 * v + i] >= 0 && vtab[5 * v + i] < (1LL << 31), op.op, ": policy word out of range");
+    t.pct[v] = (int)vtab[5 * v], t.L[v] = (int)vtab[5 * v + 1], t.M[v] = (int)vtab[5 * v + 2];
+    t.K[v] = (int)vtab[5 * v + 3], t.off[v] = (int)vtab[5 * v + 4];
+  }
+  TORCH_CHECK(ds2_speed_supported(&t, h_words), op.op,
+              ": policy outside the kernels' contract (distinct percents in 50..200, L pct == 100 M, K even and <= 320, "
+              "tables inside h, 160 KB of LDS)");
+  return t;
+}
+int* speed_plan_arg(const Op& op, const at::Tensor& plan, int64_t B) { return op.i32(plan, "plan", "B, 2", exactly(2 * B)); }
+
+// seed, step and first_utt come as 32-bit words; min_out int32 [B] or None, max_out 0: none
+void speed_plan(OptT lens, OptT min_out, at::Tensor plan, int64_t S, int64_t max_out, std::vector<int64_t> vtab,
+                int64_t seed_lo, int64_t seed_hi, int64_t step_lo, int64_t step_hi, int64_t first_utt) {
+  const Op op{"speed.plan"};
+  op.dims(plan, "plan", 2, "B, 2");
+  const int64_t B = plan.size(0);
+  TORCH_CHECK(B >= 1 && B < (1LL << 31) && S >= 1 && S < (1LL << 30) && max_out >= 0 && max_out < (1LL << 31), op.op,
+              ": B in [1, 2^31), S in [1, 2^30), max_out in [0, 2^31)");
+  const DS2SpeedTable t = speed_table(op, vtab, 1LL << 40);
+  op.launched(ds2_speed_plan(op.lens(lens, "lens", B), op.i32(min_out, "min_out", "B", exactly(B)), speed_plan_arg(op, plan, B),
+                             (int)B, (int)S, (int)max_out, &t, op.word(seed_lo, "seed_lo"), op.word(seed_hi, "seed_hi"),
+                             op.word(step_lo, "step_lo"), op.word(step_hi, "step_hi"), op.word(first_utt, "first_utt"),
+                             op.stream()));
+}
+
+// out fp32 [B, n_out], out_lens int32 [B]. tight: the caller derived n_out from the plan of a host copy of the
+// lengths; without it n_out must hold the worst case of the policy
+void speed_apply(at::Tensor x, OptT lens, at::Tensor plan, at::Tensor h, std::vector<int64_t> vtab, at::Tensor out,
+                 at::Tensor out_lens, bool tight) {
+  const Op op{"speed.apply"};
+  op.dims(x, "x", 2, "B, S");
+  op.dims(out, "out", 2, "B, n_out");
+  TORCH_CHECK(x.scalar_type() == at::kShort || x.scalar_type() == at::kFloat, op.op, ": x must be float32 or int16");
+  const int64_t B = x.size(0), S = x.size(1), n_out = out.size(1);
+  TORCH_CHECK(B >= 1 && B <= 65535 && S >= 1 && S < (1LL << 30), op.op, ": x [B, S] with B <= 65535, 1 <= S < 2^30, got ",
+              x.sizes());
+  const DS2SpeedTable t = speed_table(op, vtab, h.numel());
+  TORCH_CHECK(out.size(0) == B && n_out >= 1 && n_out < (1LL << 31) && (tight || n_out >= ds2_speed_out_width(&t, S)), op.op,
+              ": out must be fp32 [B, n_out] with n_out >= ", ds2_speed_out_width(&t, S),
+              " (the policy's worst case) unless the caller vouches for a tight width, got ", out.sizes());
+  op.launched(ds2_speed_apply(op.raw(x, "x", x.scalar_type(), "B, S", whole(x)), x.scalar_type() == at::kShort ? 1 : 0, (int)B,
+                              (int)S, op.lens(lens, "lens", B), speed_plan_arg(op, plan, B),
+                              op.f32(h, "h", "table words", whole(h), 16), h.numel(), &t,
+                              op.f32(out, "out", "B, n_out", whole(out)), (int)n_out, tight ? 1 : 0,
+                              op.i32(out_lens, "out_lens", "B", exactly(B)), op.stream()));
+}
+
 // --------------------------------------------------------------------------- summaries (csrc/stats.hip)
 // counts int32 [hist_nbucket]; part fp32 [hist_blocks(n), 6 or more]
 void hist_stats(at::Tensor x, at::Tensor counts, at::Tensor part) {
@@ -1597,5 +1655,23 @@ PYBIND11_MODULE(_C, m) {
   wa.def("apply", &waveaug_apply, py::arg("x"), py::arg("lens"), py::arg("plan"), py::arg("coef"), py::arg("data"),
          py::arg("start"), py::arg("length"), py::arg("out"));
   wa.def("segment", []() { return ds2_waveaug_segment(); });
+  // csrc/speed.hip; checked like the entries above by tests/test_speed_bindings.py
+  auto sp = m.def_submodule("speed", "speed perturbation of waveforms (csrc/speed.hip)");
+  sp.def("plan", &speed_plan, py::arg("lens"), py::arg("min_out"), py::arg("plan"), py::arg("S"), py::arg("max_out"),
+         py::arg("vtab"), py::arg("seed_lo"), py::arg("seed_hi"), py::arg("step_lo"), py::arg("step_hi"),
+         py::arg("first_utt"));
+  sp.def("apply", &speed_apply, py::arg("x"), py::arg("lens"), py::arg("plan"), py::arg("h"), py::arg("vtab"),
+         py::arg("out"), py::arg("out_lens"), py::arg("tight"));
+  sp.def("tile", []() { return ds2_speed_tile(); });
+  sp.def("supported", [](std::vector<int64_t> vtab, int64_t h_words) {
+    if (vtab.empty() || vtab.size() % 5 != 0 || vtab.size() > 40) return false;
+    DS2SpeedTable t{};
+    t.V = (int)(vtab.size() / 5);
+    for (size_t i = 0; i < vtab.size(); ++i) {
+      if (vtab[i] < 0 || vtab[i] >= (1LL << 31)) return false;
+      (i % 5 == 0 ? t.pct : i % 5 == 1 ? t.L : i % 5 == 2 ? t.M : i % 5 == 3 ? t.K : t.off)[i / 5] = (int)vtab[i];
+    }
+    return ds2_speed_supported(&t, h_words) != 0;
+  }, py::arg("vtab"), py::arg("h_words"));
 }
 

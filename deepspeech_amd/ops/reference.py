@@ -775,3 +775,94 @@ def waveaug_ref(x, lens, bank, policy, seed: int, step: int, first_utt: int = 0)
     energy = waveaug_energy_ref(x, lens, z)
     coef = waveaug_coef_ref(plan, energy)
     return waveaug_mix_ref(x, lens, plan, z, coef), plan, energy, coef
+
+
+# ---------------------------------------------------------------------------- speed perturbation (ops/speed.py, csrc/speed.hip)
+# Definition shared by the kernels, the torch composite and the tests. A policy is V distinct
+# integer percents p_0 .. p_{V-1}, 1 <= V <= 8, 50 <= p <= 200. Variant p != 100 resamples with
+# (L, M, K, h) = resample_table(in_rate=p, out_rate=100), h rounded to fp32 once; p == 100 is the
+# identity, a bit copy (never the L = M = 1 filter, which would low-pass the signal). Per
+# utterance of x [B, S] with n = clamp(lens[b], 0, S):
+#   plan   (pct, n_out) from one Philox4x32-10 block, key seed, counter (1, u, step & 0xffffffff,
+#          WAVEAUG_STREAM | (step >> 32) & 0x3fffffff), u = first_utt + b: the noise plan's stream
+#          with first word 1. v = U(x0, V), cand = ceil(n L_v / M_v) (n for the identity); the row
+#          is (p_v, cand), or (100, n) by selection when n == 0, cand < min_out[b] or
+#          (max_out > 0 and) cand > max_out
+#   y      fp32 [B, S_out]: a perturbed row is resample_ref of that row alone (one fp32 fma chain
+#          in ascending k on the device; fp64 rounded once here), an identity row fp32(x[j]);
+#          every column at or past n_out is +0 whatever x holds past n
+#   S_out  a multiple of 160: speed_out_width (the worst case over the policy), or the tight
+#          width of a plan computed from a host copy of the lengths
+SPEED_MAX_V = 8
+SPEED_MIN_PCT, SPEED_MAX_PCT = 50, 200
+SPEED_HOP = 160
+
+
+def speed_pcts(policy) -> Tuple[int, ...]:
+    return tuple(int(p) for p in getattr(policy, "pcts", policy))
+
+
+def speed_out_len(n: int, pct: int) -> int:
+    """Samples of an n-sample row played at pct percent of its speed."""
+    if int(pct) == 100:
+        return int(n)
+    g = int(np.gcd(int(pct), 100))
+    return resample_out_len(n, 100 // g, int(pct) // g)
+
+
+def speed_round_width(n: int) -> int:
+    """The smallest multiple of one hop (and at least one) that holds n samples."""
+    return max(1, -(-int(n) // SPEED_HOP)) * SPEED_HOP
+
+
+def speed_out_width(S: int, policy) -> int:
+    """The output width that holds any row of S samples under any variant of the policy (a row
+    may always fall back to the identity)."""
+    return speed_round_width(max([int(S)] + [speed_out_len(S, p) for p in speed_pcts(policy)]))
+
+
+def speed_plan_ref(lens, B: int, S: int, policy, seed: int, step: int, first_utt: int = 0, min_out=None,
+                   max_out: int = 0) -> torch.Tensor:
+    """The plan [B, 2] int32 = (pct, n_out) of utterances first_utt .. first_utt + B - 1 at ``step``,
+    in exact integer arithmetic."""
+    pcts = speed_pcts(policy)
+    n = waveaug_lens(lens, B, S)
+    u = (int(first_utt) + np.arange(B, dtype=np.uint64)) & np.uint64(0xffffffff)
+    x = philox4x32((np.uint64(1), u, np.uint64(step & 0xffffffff),
+                    np.uint64(WAVEAUG_STREAM | ((step >> 32) & 0x3fffffff))),
+                   (np.uint64(seed & 0xffffffff), np.uint64((seed >> 32) & 0xffffffff)))
+    x0 = np.broadcast_to(x[0], (B,)).astype(np.uint64)
+    v = ((x0 * np.uint64(len(pcts))) >> np.uint64(32)).astype(np.int64)
+    pct = np.asarray(pcts, np.int64)[v]
+    cand = np.array([speed_out_len(int(n[b]), int(pct[b])) for b in range(B)], np.int64)
+    lo = np.zeros(B, np.int64) if min_out is None else \
+        np.asarray(torch.as_tensor(min_out).cpu()).astype(np.int64).reshape(-1)
+    back = (n == 0) | (cand < lo) | ((int(max_out) > 0) & (cand > int(max_out)))
+    plan = np.stack([np.where(back, 100, pct), np.where(back, n, cand)], 1)
+    return torch.from_numpy(plan.astype(np.int32))
+
+
+def speed_ref(x, lens, plan, out_width: int, return_abs: bool = False):
+    """(y fp32 [B, out_width], out_lens int32 [B]) of the definition from a plan; ``return_abs``:
+    (y64, a64, out_lens), the fp64 values and sum_k |h x| per output (|x| on identity rows)."""
+    xv = np.asarray(torch.as_tensor(x).cpu())
+    B, S = xv.shape
+    n = waveaug_lens(lens, B, S)
+    plan = np.asarray(torch.as_tensor(plan).cpu()).astype(np.int64)
+    W = int(out_width)
+    y = np.zeros((B, W), np.float64)
+    a = np.zeros((B, W), np.float64)
+    cnt = np.zeros(B, np.int32)
+    for b in range(B):
+        pct, c = int(plan[b, 0]), int(min(max(plan[b, 1], 0), W))
+        row = xv[b, :n[b]].astype(np.float64)
+        if pct == 100:
+            c = min(c, int(n[b]))
+            y[b, :c], a[b, :c] = row[:c], np.abs(row[:c])
+        elif c > 0:
+            r, ra = resample_ref(row, pct, 100, return_abs=True)
+            y[b, :c], a[b, :c] = r[:c], ra[:c]
+        cnt[b] = c
+    if return_abs:
+        return y, a, torch.from_numpy(cnt)
+    return torch.from_numpy(y.astype(np.float32)), torch.from_numpy(cnt)

@@ -96,16 +96,18 @@ def build_data(args, ctx, train_dir):
 
 def build_front_end(args, data, dev, is_main: bool = True):
     """The per-step audio front end (data/audio_batch.py) of a source that serves raw audio (an
-    audio store, detected from its index, or --dummy_audio), else None. --wave_aug needs one."""
+    audio store, detected from its index, or --dummy_audio), else None. --wave_aug and
+    --speed_perturb need one."""
     index = getattr(data, "index", None)
     audio = bool(args.dummy_audio) if args.dummy else bool(index is not None and index.is_audio)
     if not audio:
-        if args.wave_aug:
-            if hasattr(data, "close"):
-                data.close()
-            raise ValueError("--wave_aug acts on waveforms, and this run reads stored feature frames: write an "
-                             "audio store with `python -m deepspeech_amd.data.preprocess --store audio` "
-                             "(or use --dummy True --dummy_audio True)")
+        for flag in ("wave_aug", "speed_perturb"):
+            if getattr(args, flag):
+                if hasattr(data, "close"):
+                    data.close()
+                raise ValueError("--%s acts on waveforms, and this run reads stored feature frames: write an "
+                                 "audio store with `python -m deepspeech_amd.data.preprocess --store audio` "
+                                 "(or use --dummy True --dummy_audio True)" % flag)
         return None
     from .data.audio_batch import AudioFrontEnd
     wave_aug = None
@@ -117,9 +119,17 @@ def build_front_end(args, data, dev, is_main: bool = True):
         wave_aug = WaveAugment(policy, NoiseBank.from_policy(policy, args.seed), args.seed)
         if is_main:
             print("wave_aug: ", policy, "(%d clips)" % len(wave_aug.bank))
+    speed = None
+    if args.speed_perturb:
+        # a ratio drawn per (seed, global step, global utterance index), on the noise plan's Philox
+        # stream with another first counter word
+        from .ops.speed import SpeedPerturb, SpeedPolicy
+        speed = SpeedPerturb(SpeedPolicy.parse(args.speed_perturb), args.seed)
+        if is_main:
+            print("speed_perturb: ", speed.policy)
     if is_main:
         print("audio_features: ", args.audio_features)
-    return AudioFrontEnd(args.audio_features, dev, wave_aug)
+    return AudioFrontEnd(args.audio_features, dev, wave_aug, speed, args.max_frames)
 
 
 def write_debug_reports(prof, model, args, dev) -> None:
@@ -223,7 +233,8 @@ def main(argv=None) -> int:
     if args.engine in ("mkldnn_rnn", "cudnn_rnn") and model.cell == "rnn_relu" and model.layout == "nchw":
         model.param_layout = "mkldnn"
     data, steps_per_epoch = build_data(args, ctx, args.train_dir)
-    # --wave_aug: a training hyper-parameter like --specaug (not restored, never read by evaluation)
+    # --wave_aug, --speed_perturb: training hyper-parameters like --specaug (not restored, never read
+    # by evaluation)
     front = build_front_end(args, data, dev, ctx.is_main)
     trainer = Trainer(model, lr_schedule_from_args(args, steps_per_epoch), args.moving_avg_decay,
                       world_size=ctx.world_size, bucket_mb=args.bucket_mb,
@@ -289,7 +300,7 @@ def main(argv=None) -> int:
             hb_ = data.next()
             return collapse_batch_labels(hb_) if args.ctc_collapse_repeated else hb_
     src = _Src()
-    wave_on = front is not None and front.wave_aug is not None
+    wave_on = front is not None and (front.wave_aug is not None or front.speed is not None)
     if (aug is not None or wave_on or model.rnn_dropout_thr > 0) and args.dummy and start > 0:
         # an augmented synthetic run resumes its feed too (the generators are cheap to replay), so
         # its steps are those of the uninterrupted run: the same batch under the same masks
@@ -320,8 +331,9 @@ def main(argv=None) -> int:
         if batch is None:
             batch = to_device(hb, dev)
         if front is not None:
-            # wave augmentation, featurize, then SpecAugment: all outside the step graphs
-            batch = front(batch, step, first_utt=ctx.rank * args.batch_size, training=True)
+            # speed and noise augmentation, featurize, then SpecAugment: all outside the step graphs;
+            # the host batch's lengths give speed perturbation its tight output width
+            batch = front(batch, step, first_utt=ctx.rank * args.batch_size, training=True, host=hb)
         if aug is not None:
             batch = dict(batch, feats=aug(batch["feats"], batch["seq_lens"], step,
                                           first_utt=ctx.rank * args.batch_size))
