@@ -193,18 +193,20 @@ int ds2_fc_logits(const void* h, const void* W, const void* bias, void* logits, 
                   hipStream_t st);
 int ds2_ctc_greedy(const void* logits, int bf16, const int* lens, int T, int N, int K, int blank,
                    int* labels, int* counts, float* score, hipStream_t st);
+// key [B][W][2]: 64-bit fingerprints of each hypothesis' prefix and of its parent's, the beams'
+// prefix identity (zero at reset; csrc/beam.hip). -51: no key buffer.
 int ds2_ctc_beam(const float* lp, const int* frames, int T, int B, int K, int W, int blank, float prune, int* node,
                  int* last, int* parent, float* pb, float* pnb, int* nbeam, void* nodes, int* nnodes, int cap,
-                 unsigned* err, hipStream_t st);
+                 unsigned* err, unsigned long long* key, hipStream_t st);
 int ds2_ctc_beam_backtrack(const void* nodes, int cap, const int* node, const int* nbeam, const float* pb,
                            const float* pnb, int B, int W, int* out, int* out_len, float* score, int Lcap,
                            hipStream_t st);
-// LM shallow fusion: lm [S][K] int2 rows (w fp32 bits, next state), lmstate [B][W] int32, lmkey
-// [B][W][2] 64-bit prefix fingerprints (own, parent's; zero at reset); the backtrack adds the
-// </s> weight (column blank) to every score (final mode). -51: bad LM arguments.
+// LM shallow fusion: lm [S][K] int2 rows (w fp32 bits, next state), lmstate [B][W] int32, key as
+// above; the backtrack adds the </s> weight (column blank) to every score (final mode). -51: bad
+// LM arguments.
 int ds2_ctc_beam_lm(const float* lp, const int* frames, int T, int B, int K, int W, int blank, float prune, int* node,
                     int* last, int* parent, float* pb, float* pnb, int* nbeam, void* nodes, int* nnodes, int cap,
-                    unsigned* err, const void* lm, int S, int* lmstate, unsigned long long* lmkey, hipStream_t st);
+                    unsigned* err, const void* lm, int S, int* lmstate, unsigned long long* key, hipStream_t st);
 int ds2_ctc_beam_backtrack_lm(const void* nodes, int cap, const int* node, const int* nbeam, const float* pb,
                               const float* pnb, int B, int W, int* out, int* out_len, float* score, int Lcap,
                               const void* lm, int S, int K, int blank, const int* lmstate, hipStream_t st);

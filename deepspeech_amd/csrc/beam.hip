@@ -7,10 +7,11 @@
 // on the device between chunks and one wave64 decodes one stream:
 //
 //   * lane i < nbeam holds hypothesis i (trie node, last label, parent node, log p ending in
-//     blank / non-blank); lane k < K holds class k's log-prob of the frame;
+//     blank / non-blank, and the 64-bit fingerprints of its prefix and of its parent's prefix);
+//     lane k < K holds class k's log-prob of the frame;
 //   * merging needs no hash map: distinct hypotheses have distinct prefixes, so the extension
 //     of hypothesis j by label k reaches an existing prefix only when some hypothesis i has
-//     parent(i) == node(j) and last(i) == k; it then adds into i's "stay" entry (CPU: the
+//     parent_key(i) == key(j) and last(i) == k; it then adds into i's "stay" entry (CPU: the
 //     same get(node) slot), otherwise it is a new prefix whose trie node is created only if it
 //     survives the top-W selection;
 //   * lane k scores the W extensions by class k (the hypotheses broadcast with readlane), the
@@ -23,6 +24,18 @@
 // to the ulps of expf / log1pf. Reference semantics: tf.nn.ctc_beam_search_decoder (the
 // reference itself decodes greedily, src/deepSpeech_test.py:212-215).
 //
+// Prefix identity. A prefix is identified by its fingerprint, never by its trie node: key of a
+// prefix = mix(key of its parent, label), key of the empty prefix = 0, carried in lane registers
+// and stored beside the beam state between launches (registers only, no loads in the frame loop).
+// A trie node id does not identify a live prefix: when a prefix P is pruned while a longer
+// Q = P + x stays live and P is then created again from its own parent, P gets a fresh node and Q
+// still points to the old one; a node-id test then no longer sees that P + x is Q, the beam holds Q
+// twice and Q's probability is split. Small alphabets meet this within tens of frames (K = 3,
+// W = 3), and LM weights reorder a K = 29 beam enough to meet it within 30 frames
+// (tests/beam_cases.py, the stale cases). The trie nodes are only what the backtrack walks: two
+// nodes of one prefix spell the same labels. Two different live prefixes one label apart collide
+// with probability 2^-64 per comparison.
+//
 // Shallow LM fusion (ctc_beam_kernel<true>; deepspeech_amd/lm.py): the LM is a backoff-expanded
 // automaton packed as int2 rows lm[state][k] = (w, next) with w = alpha * ln P(k | state) + beta
 // as fp32 bits. Each hypothesis carries its state in a lane register beside its node; at the top
@@ -30,17 +43,7 @@
 // latency overlaps the merge scan and the frame's own log-prob load), every extension term gets
 // (base + p) + w, and when (j, k) is selected the survivor's state is a readlane of the `next`
 // lane k already holds: nothing loads inside the serial selection. The <false> instantiation is
-// the acoustic search as it was.
-//
-// Prefix identity with an LM. The node-id test above ("parent(i) == node(j)") assumes that a live
-// prefix has one trie node. That breaks when a prefix P is pruned while a longer Q = P + x stays
-// live and P is then created again from its own parent: P gets a fresh node, Q still points to
-// the old one, the extension of P by x no longer finds Q and the beam holds Q twice. The acoustic
-// search meets this rarely; LM weights reorder the beam enough to meet it within 30 frames
-// (W = 8). So <true> identifies prefixes by a 64-bit fingerprint carried beside the LM state
-// (key of a prefix = mix(key of its parent, label), key of the empty prefix = 0) and compares
-// (key, parent key) where <false> compares (node, parent node): registers only, no loads. Two
-// different live prefixes one label apart collide with probability 2^-64 per comparison.
+// the same search without the LM terms.
 #include "common.h"
 
 using namespace ds2;
@@ -71,9 +74,9 @@ struct BeamArgs {
   int* nnodes;         // [B] nodes used
   int cap;
   unsigned* err;       // bit 1: node table full (host sizes it: 1 + W * frames)
+  unsigned long long* key;     // [B][W][2] fingerprint of each hypothesis' prefix and of its parent's
   const int2* lm;      // LM only: [S][K] (w fp32 bits, next state; column blank: (w of </s>, -1))
   int* lmstate;        // LM only: [B][W] LM state of each hypothesis
-  unsigned long long* lmkey;   // LM only: [B][W][2] fingerprint of each hypothesis' prefix and of its parent's
   int S;
 };
 
@@ -107,13 +110,11 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
   int h_state = 0;
   unsigned long long h_key = 0ull, h_pkey = 0ull;
   if constexpr (LM) {
-    if (lane < nb) {
-      h_state = min(max(a.lmstate[bo + lane], 0), a.S - 1);
-      h_key = a.lmkey[(bo + lane) * 2];
-      h_pkey = a.lmkey[(bo + lane) * 2 + 1];
-    }
+    if (lane < nb) h_state = min(max(a.lmstate[bo + lane], 0), a.S - 1);
   }
   if (lane < nb) {
+    h_key = a.key[(bo + lane) * 2];
+    h_pkey = a.key[(bo + lane) * 2 + 1];
     h_node = a.node[bo + lane];
     h_last = a.last[bo + lane];
     h_par = a.parent[bo + lane];
@@ -146,20 +147,19 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
     const unsigned long long cmask = __ballot(lane < K && p >= mx + a.prune);
     const bool live = lane < nb;
     const float tot = live ? log_add(h_pb, h_pnb) : -INFINITY;
-    // merge source of my hypothesis (the one whose extension by my last label is my prefix),
-    // and the labels whose extension of MY prefix lands on an existing hypothesis
+    // merge source of my hypothesis: the live hypothesis whose prefix is my prefix' parent, so
+    // that its extension by my last label is my prefix (h_last < 0: the empty prefix has none)
     int msrc = -1;
-    unsigned long long mmask = 0ull;
     for (int i = 0; i < nb; ++i) {
-      const int ni = bcast(h_node, i), pi = bcast(h_par, i), li = bcast(h_last, i);
-      if constexpr (LM) {
-        const unsigned long long ki = bcast(h_key, i), pki = bcast(h_pkey, i);
-        if (live && h_par >= 0 && ki == h_pkey) msrc = i;
-        if (pi >= 0 && pki == h_key && live) mmask |= 1ull << li;
-      } else {
-        if (live && h_par >= 0 && ni == h_par) msrc = i;
-        if (pi >= 0 && pi == h_node && live) mmask |= 1ull << li;
-      }
+      const unsigned long long ki = bcast(h_key, i);
+      if (live && h_last >= 0 && ki == h_pkey) msrc = i;
+    }
+    // the same relation seen from the class lanes: bit j of lane k says that the extension of
+    // hypothesis j by class k is an existing hypothesis (it merges into that one's stay entry)
+    unsigned kmask = 0u;
+    for (int i = 0; i < nb; ++i) {
+      const int mi = bcast(msrc, i), li = bcast(h_last, i);
+      if (mi >= 0 && li == lane) kmask |= 1u << mi;
     }
     // LM weight of the merged extension: row state(msrc), column my last label
     float m_w = 0.f;
@@ -195,12 +195,10 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
       if (j < nb) {
         const float tj = bcast(tot, j), pj = bcast(h_pb, j);
         const int lj = bcast(h_last, j);
-        const unsigned long long mj = ((unsigned long long)(unsigned)bcast((int)(mmask >> 32), j) << 32) |
-                                      (unsigned)bcast((int)mmask, j);
         if constexpr (LM) {
-          if (kc && !((mj >> lane) & 1ull)) ext[j] = ((lane == lj ? pj : tj) + p) + __int_as_float(wn[j].x);
+          if (kc && !((kmask >> j) & 1u)) ext[j] = ((lane == lj ? pj : tj) + p) + __int_as_float(wn[j].x);
         } else {
-          if (kc && !((mj >> lane) & 1ull)) ext[j] = (lane == lj ? pj : tj) + p;
+          if (kc && !((kmask >> j) & 1u)) ext[j] = (lane == lj ? pj : tj) + p;
         }
       }
     }
@@ -209,7 +207,8 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
     int n_node = 0, n_last = -1, n_par = -1;
     float n_pb = -INFINITY, n_pnb = -INFINITY;
     int n_state = 0;
-    unsigned long long n_key = 0ull, n_pkey = 0ull;
+    int n_src = 0;                                     // the hypothesis my survivor stays on or extends
+    bool n_ext = false;
     for (int r = 0; r < W; ++r) {
       float best = stay;
       int bid = live ? lane : 0x7fffffff;
@@ -237,15 +236,11 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
         const int nj = bcast(h_node, j), lj = bcast(h_last, j), pj = bcast(h_par, j);
         const float bj = bcast(s_pb, j), qj = bcast(s_pnb, j);
         if constexpr (LM) {
-          const int sj = bcast(h_state, j);            // a stay keeps its state and keys
-          const unsigned long long kj = bcast(h_key, j), pkj = bcast(h_pkey, j);
-          if (lane == r) {
-            n_state = sj;
-            n_key = kj;
-            n_pkey = pkj;
-          }
+          const int sj = bcast(h_state, j);            // a stay keeps its state
+          if (lane == r) n_state = sj;
         }
         if (lane == r) {
+          n_src = j;
           n_node = nj;
           n_last = lj;
           n_par = pj;
@@ -265,17 +260,14 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
           for (int q = 0; q < BM_MAXW; ++q)
             if (q == j) nx = wn[q].y;
           const int sk = min(max(bcast(nx, k), 0), a.S - 1);   // lane k holds next(state_j, k)
-          const unsigned long long kj = bcast(h_key, j);
-          if (lane == r) {
-            n_state = sk;
-            n_key = key_extend(kj, k);
-            n_pkey = kj;
-          }
+          if (lane == r) n_state = sk;
         }
         const int nj = bcast(h_node, j);
         const int id = nn + newn;
         ++newn;
         if (lane == r) {
+          n_src = j;
+          n_ext = true;
           n_node = id;
           n_last = k;
           n_par = nj;
@@ -286,6 +278,11 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
       }
       ++nsel;
     }
+    // the survivors' keys, every lane at once (nothing of this in the serial selection): a stay
+    // keeps its keys, the extension of j by k gets (key_extend(key_j, k), key_j)
+    const unsigned long long kj = __shfl(h_key, n_src, 64), pkj = __shfl(h_pkey, n_src, 64);
+    const unsigned long long n_key = lane >= nsel ? 0ull : n_ext ? key_extend(kj, n_last) : kj;
+    const unsigned long long n_pkey = lane >= nsel ? 0ull : n_ext ? kj : pkj;
     nb = nsel;
     nn += newn;
     h_node = n_node;
@@ -293,20 +290,16 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
     h_par = n_par;
     h_pb = n_pb;
     h_pnb = n_pnb;
-    if constexpr (LM) {
-      h_state = n_state;
-      h_key = n_key;
-      h_pkey = n_pkey;
-    }
+    h_key = n_key;
+    h_pkey = n_pkey;
+    if constexpr (LM) h_state = n_state;
   }
   if constexpr (LM) {
-    if (lane < W) {
-      a.lmstate[bo + lane] = h_state;
-      a.lmkey[(bo + lane) * 2] = h_key;
-      a.lmkey[(bo + lane) * 2 + 1] = h_pkey;
-    }
+    if (lane < W) a.lmstate[bo + lane] = h_state;
   }
   if (lane < W) {
+    a.key[(bo + lane) * 2] = h_key;
+    a.key[(bo + lane) * 2 + 1] = h_pkey;
     a.node[bo + lane] = h_node;
     a.last[bo + lane] = h_last;
     a.parent[bo + lane] = h_par;
@@ -351,27 +344,27 @@ __global__ __launch_bounds__(64) void ctc_beam_backtrack_kernel(const int2* node
 
 extern "C" int ds2_ctc_beam(const float* lp, const int* frames, int T, int B, int K, int W, int blank, float prune,
                             int* node, int* last, int* parent, float* pb, float* pnb, int* nbeam, void* nodes,
-                            int* nnodes, int cap, unsigned* err, hipStream_t st) {
+                            int* nnodes, int cap, unsigned* err, unsigned long long* key, hipStream_t st) {
   if (K < 2 || K > 64 || W < 1 || W > BM_MAXW || blank < 0 || blank >= K || B < 1 || T < 0 || cap < 1) return -50;
+  if (key == nullptr) return -51;
   if (T == 0) return 0;
   BeamArgs a{lp, frames, T, B, K, W, blank, prune, node, last, parent, pb, pnb, nbeam,
-             static_cast<int2*>(nodes), nnodes, cap, err, nullptr, nullptr, nullptr, 0};
+             static_cast<int2*>(nodes), nnodes, cap, err, key, nullptr, nullptr, 0};
   ds2_launch(ctc_beam_kernel<false>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a);
   return (int)hipGetLastError();
 }
 
-// the same search with the LM automaton lm [S][K] int2, the per-hypothesis states lmstate [B][W]
-// and prefix fingerprints lmkey [B][W][2]
+// the same search with the LM automaton lm [S][K] int2 and the per-hypothesis states lmstate [B][W]
 extern "C" int ds2_ctc_beam_lm(const float* lp, const int* frames, int T, int B, int K, int W, int blank, float prune,
                                int* node, int* last, int* parent, float* pb, float* pnb, int* nbeam, void* nodes,
                                int* nnodes, int cap, unsigned* err, const void* lm, int S, int* lmstate,
-                               unsigned long long* lmkey, hipStream_t st) {
+                               unsigned long long* key, hipStream_t st) {
   if (K < 2 || K > 64 || W < 1 || W > BM_MAXW || blank < 0 || blank >= K || B < 1 || T < 0 || cap < 1) return -50;
-  if (lm == nullptr || lmstate == nullptr || lmkey == nullptr || S < 1 || (long long)S * K >= (1ll << 31))
+  if (lm == nullptr || lmstate == nullptr || key == nullptr || S < 1 || (long long)S * K >= (1ll << 31))
     return -51;
   if (T == 0) return 0;
   BeamArgs a{lp, frames, T, B, K, W, blank, prune, node, last, parent, pb, pnb, nbeam,
-             static_cast<int2*>(nodes), nnodes, cap, err, static_cast<const int2*>(lm), lmstate, lmkey, S};
+             static_cast<int2*>(nodes), nnodes, cap, err, key, static_cast<const int2*>(lm), lmstate, S};
   ds2_launch(ctc_beam_kernel<true>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, a);
   return (int)hipGetLastError();
 }

@@ -804,8 +804,8 @@ BeamState beam_state(const Op& op, const at::Tensor& node, const at::Tensor& las
           op.i32(nnodes, "nnodes", "B", b), op.f32(pb, "pb", "B, W", bw), op.f32(pnb, "pnb", "B, W", bw)};
 }
 
-// LM shallow fusion (deepspeech_amd/lm.py): lm [S, K, 2] int32 (w fp32 bits, next state),
-// lmstate [B, W] int32 and lmkey [B, W, 2] int64 (prefix fingerprints) beside the beam state
+// LM shallow fusion (deepspeech_amd/lm.py): lm [S, K, 2] int32 (w fp32 bits, next state) and
+// lmstate [B, W] int32 beside the beam state
 struct BeamLm {
   const int* lm = nullptr;
   int S = 0, K = 0;
@@ -820,9 +820,10 @@ BeamLm beam_lm(const Op& op, const at::Tensor& lm, const at::Tensor& lmstate, co
 }
 
 // advance the beams by the frames of lp [T, B, K] (fp32 log-probs; frames [B] int32 per-stream frame
-// counts, or all T); with an LM triple, fused with its weights
+// counts, or all T); key [B, W, 2] int64: the hypotheses' prefix fingerprints (zero at reset); with
+// an LM pair, fused with its weights
 void ctc_beam_any(const Op& op, const at::Tensor& lp, const OptT& frames, int64_t blank, double prune, const BeamState& s,
-                  const at::Tensor& err, const at::Tensor* lm, const at::Tensor* lmstate, const at::Tensor* lmkey) {
+                  const at::Tensor& err, const at::Tensor& key, const at::Tensor* lm, const at::Tensor* lmstate) {
   op.dims(lp, "lp", 3, "T, B, K");
   const int T = (int)lp.size(0), K = (int)lp.size(2);
   TORCH_CHECK(lp.size(1) == s.B && K >= 2 && K <= 64 && blank >= 0 && blank < K, op.op,
@@ -830,30 +831,30 @@ void ctc_beam_any(const Op& op, const at::Tensor& lp, const OptT& frames, int64_
   const float* lpp = op.f32(lp, "lp", "T, B, K", whole(lp));
   const int* fr = op.lens(frames, "frames", s.B);
   unsigned* e = op.u32(err, "err", "1", at_least(1));
+  auto* k = reinterpret_cast<unsigned long long*>(op.i64(key, "key", "B, W, 2", exactly((int64_t)s.B * s.W * 2)));
   if (!lm) {
     op.launched(ds2_ctc_beam(lpp, fr, T, s.B, K, s.W, (int)blank, (float)prune, s.node, s.last, s.parent, s.pb, s.pnb, s.nbeam,
-                             s.nodes, s.nnodes, s.cap, e, op.stream()));
+                             s.nodes, s.nnodes, s.cap, e, k, op.stream()));
     return;
   }
   const BeamLm l = beam_lm(op, *lm, *lmstate, s);
   TORCH_CHECK(l.K == K, op.op, ": lm must be int32 [S, K, 2] over lp's K classes");
-  auto* key = reinterpret_cast<unsigned long long*>(op.i64(*lmkey, "lmkey", "B, W, 2", exactly((int64_t)s.B * s.W * 2)));
   op.launched(ds2_ctc_beam_lm(lpp, fr, T, s.B, K, s.W, (int)blank, (float)prune, s.node, s.last, s.parent, s.pb, s.pnb, s.nbeam,
-                              s.nodes, s.nnodes, s.cap, e, l.lm, l.S, l.lmstate, key, op.stream()));
+                              s.nodes, s.nnodes, s.cap, e, l.lm, l.S, l.lmstate, k, op.stream()));
 }
 void ctc_beam(at::Tensor lp, OptT frames, int64_t blank, double prune, at::Tensor node, at::Tensor last,
               at::Tensor parent, at::Tensor pb, at::Tensor pnb, at::Tensor nbeam, at::Tensor nodes,
-              at::Tensor nnodes, at::Tensor err) {
+              at::Tensor nnodes, at::Tensor err, at::Tensor key) {
   const Op op{"ctc_beam"};
-  ctc_beam_any(op, lp, frames, blank, prune, beam_state(op, node, last, parent, pb, pnb, nbeam, nodes, nnodes), err,
-               nullptr, nullptr, nullptr);
+  ctc_beam_any(op, lp, frames, blank, prune, beam_state(op, node, last, parent, pb, pnb, nbeam, nodes, nnodes), err, key,
+               nullptr, nullptr);
 }
 void ctc_beam_lm(at::Tensor lp, OptT frames, int64_t blank, double prune, at::Tensor node, at::Tensor last,
                  at::Tensor parent, at::Tensor pb, at::Tensor pnb, at::Tensor nbeam, at::Tensor nodes,
-                 at::Tensor nnodes, at::Tensor err, at::Tensor lm, at::Tensor lmstate, at::Tensor lmkey) {
+                 at::Tensor nnodes, at::Tensor err, at::Tensor lm, at::Tensor lmstate, at::Tensor key) {
   const Op op{"ctc_beam_lm"};
-  ctc_beam_any(op, lp, frames, blank, prune, beam_state(op, node, last, parent, pb, pnb, nbeam, nodes, nnodes), err, &lm,
-               &lmstate, &lmkey);
+  ctc_beam_any(op, lp, frames, blank, prune, beam_state(op, node, last, parent, pb, pnb, nbeam, nodes, nnodes), err, key,
+               &lm, &lmstate);
 }
 
 // labels [B, W, Lcap] (back-aligned prefix walk: the first out_len entries), out_len [B, W] (-1:

@@ -115,6 +115,9 @@ class GpuBeamSearch:
         self.nnodes = torch.empty(self.B, **i32)
         self.nodes = torch.zeros(self.B, self.cap, 2, **i32)
         self.err = torch.zeros(1, **i32)
+        # 64-bit fingerprints of each hypothesis' prefix and of its parent's: the beams' prefix
+        # identity (csrc/beam.hip)
+        self.key = torch.empty(self.B, self.W, 2, device=self.dev, dtype=torch.int64)
         self.lm = None
         if lm is not None:
             w, nxt, start = lm_tables(lm, lm_weight, label_bonus, self.blank)
@@ -126,8 +129,6 @@ class GpuBeamSearch:
             self.lm = torch.from_numpy(np.ascontiguousarray(packed)).to(self.dev)
             self.lm_start = int(start)
             self.lmstate = torch.empty(self.B, self.W, **i32)
-            # 64-bit fingerprints of each hypothesis' prefix and of its parent's (csrc/beam.hip)
-            self.lmkey = torch.empty(self.B, self.W, 2, device=self.dev, dtype=torch.int64)
         self.reset()
 
     def reset(self) -> None:
@@ -140,9 +141,9 @@ class GpuBeamSearch:
         self.pnb.fill_(float("-inf"))
         self.nbeam.fill_(1)
         self.nnodes.fill_(1)
+        self.key.zero_()
         if self.lm is not None:
             self.lmstate.fill_(self.lm_start)
-            self.lmkey.zero_()
         self.frames = 0          # frames fed so far (upper bound over streams): sizes the trie
 
     def _ensure(self, more: int) -> None:
@@ -176,10 +177,10 @@ class GpuBeamSearch:
                 raise ValueError("GpuBeamSearch.feed: lp has %d classes, the LM %d" % (lp.shape[2], self.lm.shape[1]))
             _ext.ext().ctc_beam_lm(lp, fr, self.blank, self.prune, self.node, self.last, self.parent, self.pb,
                                    self.pnb, self.nbeam, self.nodes, self.nnodes, self.err, self.lm, self.lmstate,
-                                   self.lmkey)
+                                   self.key)
         else:
             _ext.ext().ctc_beam(lp, fr, self.blank, self.prune, self.node, self.last, self.parent, self.pb,
-                                self.pnb, self.nbeam, self.nodes, self.nnodes, self.err)
+                                self.pnb, self.nbeam, self.nodes, self.nnodes, self.err, self.key)
         self.frames += T
 
     def results(self, final: bool = False) -> List[List[Tuple[List[int], float]]]:

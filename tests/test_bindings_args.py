@@ -91,7 +91,7 @@ def _beam(lm=False):
 
 def _ctc_beam(lm):
     B, W, st = _beam()
-    tail = (z(I32, 3, CK, 2), z(I32, B, W), z(I64, B, W, 2)) if lm else ()
+    tail = (z(I32, 3, CK, 2), z(I32, B, W), z(I64, B, W, 2)) if lm else (z(I64, B, W, 2),)
     return (z(F32, CT, B, CK), None, 0, 1e-4) + st + (z(I32, 1),) + tail
 
 
